@@ -1,6 +1,18 @@
 """Benchmark: verified signature sets/sec at 8192-set batches (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--inflight B] [--no-cpu-baseline] [--no-block-import]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--inflight B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-block-import] [--no-epoch-sweep] [--node-shape on]
+
+A plain run sets up (three single calls size the buffers: `p50_batch_latency_ms_unloaded`),
+warms up, times the steps and prints the JSON line of the headline; every other measurement
+(the isolated roofline call, configs 2, 3 and 5, the mainnet-shaped leg, the node-shape leg,
+the CPU baseline) runs under --full only.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, DIR/verdicts.npy:
+the per-job verdict codes of that bgv_verify call (1 valid, 0 invalid, < 0 undecodable) as
+float32, one per job of the batch.  The inputs are a function of the arguments alone (seeded
+corruption, deterministic keys, roots and signatures), so two builds can be compared output
+for output.
 
 A step = one pass of the hot path over one synthetic batch: bgv_verify of 8192
 signature sets (config 4: gossip shape, 8192 batchable one-set jobs, 1 %
@@ -16,7 +28,15 @@ against the expected codes (known by construction, the corruption classes pinned
 tests/test_gpu_parity.py).  The process group is RCCL ("nccl") when the ranks drive distinct
 GPUs, gloo for the one-GPU rehearsal (BGV_BENCH_DEVICE) and on CPU.
 
-The JSON line carries:
+--steps K times exactly K calls: the window runs from the W-th completion, a super-batch
+boundary, to the (W+K)-th, and `ms_per_step` is the window divided by K (`timed_steps` = K).
+Calls of one super-batch complete together and each dispatcher keeps one super-batch in flight,
+so completions come in bursts with a period of dispatchers x calls per super-batch (32 calls at
+the default geometry).  A K that is a multiple of the period (the default 64) ends the window on
+a period boundary; any other K ends it with the burst that holds the K-th call, which also did
+the device work of that burst's other calls, so the figure reads low by up to one period's time.
+
+Under --full the JSON line also carries:
   roofline     integer-VALU roofline of the dominant kernel: algorithmic u32 MACs
                (Fp-mul-eq counted in profiles/opcounts.json x 288) / its HIP-event time,
                against the gfx950 peak v_mad_u64_u32 rate (16 lanes/clk/SIMD x 1024 SIMDs x 2.4 GHz)
@@ -502,8 +522,9 @@ def super_batch_calls(nsets, max_slots=None):
 
 
 def timed_calls(steps, bcalls, dispatchers=2):
-    """Calls inside the timed window: the requested steps rounded up to whole completion
-    periods.  Calls of one super-batch complete together and the library keeps one super-batch
+    """Calls inside the timed window of the --full legs (mainnet-shaped, node shape), whose step
+    counts are fixed: the steps rounded up to whole completion periods (the headline times exactly
+    --steps calls).  Calls of one super-batch complete together and the library keeps one super-batch
     in flight per dispatcher, so completions repeat with a period of bcalls * dispatchers calls;
     a window that ends inside a burst would count calls whose device time it does not hold.
     steps a multiple of the period (64 at the default geometry) are timed exactly."""
@@ -543,6 +564,8 @@ def stream_window(step, expect, warmup, steps, inflight, settle_s=0.0, boundary=
             with lock:
                 done.append((t, t - ts, s, got == expect))
                 n = len(done)
+                if st["warm"] is not None and n <= st["warm"] + steps:
+                    st["last"] = got  # the latest output inside the window
                 if (st["warm"] is None and n >= warmup and n % boundary == 0
                         and t - t_begin >= settle_s):
                     st["warm"] = n
@@ -564,7 +587,7 @@ def stream_window(step, expect, warmup, steps, inflight, settle_s=0.0, boundary=
     t0 = done[warmup - 1][0] if warmup else t_begin
     window = done[warmup:target]
     return {"elapsed": window[-1][0] - t0, "latencies": [d[1] for d in window], "stats": [d[2] for d in window],
-            "calls_total": len(done), "warm_calls": warmup}
+            "calls_total": len(done), "warm_calls": warmup, "last_output": st.get("last")}
 
 
 EPOCH_SETS = 1 << 20
@@ -732,6 +755,42 @@ def roofline_isolated(ctx, native, nkeys):
     return {"sets": n, "kernel_ms": {name: statistics.median(v) for name, v in ms.items()}}
 
 
+def roofline_record(roof, opc, per_set, pipeline_frac):
+    """The `roofline` entry of the JSON line from the isolated call (roofline_isolated) and the
+    counted work per set (profiles/opcounts.json)."""
+    # dominant kernel at full occupancy, alone on the device (roofline_isolated): its
+    # algorithmic MACs (set pairs + the group pairs on the same launch) / its HIP-event time
+    rk = roof["kernel_ms"]
+    dom = max(per_set, key=lambda k: rk.get(k, 0))
+    ngr = roof["sets"] // 64
+    work = {"k_miller": roof["sets"] * opc["k_miller"] + ngr * opc["k_final[group sig pair]"],
+            "k_prep": roof["sets"] * per_set["k_prep"]}[dom]
+    achieved = work * MACS_PER_FP_MUL / (rk[dom] * 1e-3)
+    # HBM bytes of that same launch from the committed PMC passes (TRAFFIC_FILE:
+    # (FETCH_SIZE x 2 + WRITE_SIZE) x 1024, rocprofv3 reports KB) and the algorithmic bytes
+    traffic = hbm_gbs = None
+    tf = os.path.join(ROOT, TRAFFIC_FILE)
+    if os.path.exists(tf):
+        rec = json.load(open(tf)).get(dom, {})
+        if rec.get("sets") == roof["sets"]:
+            traffic = rec["bytes_per_launch"]
+            hbm_gbs = traffic / (rk[dom] * 1e-3) / 1e9
+    alg_bytes = {"k_miller": roof["sets"] * (112 + 336 + 672 + 8 + 160) + ngr * (336 + 672),
+                 "k_prep": roof["sets"] * (160 + 4 + 112 * 1 + 336 * 2 + 112 + 8)}[dom]
+    return {"bound": "valu", "kernel": dom, "achieved": achieved / 1e12, "peak": PEAK_MAC_PER_S / 1e12,
+            "unit": "TMAC/s (u32 mad)", "frac": achieved / PEAK_MAC_PER_S, "traffic": traffic,
+            "measured": "one %d-set verify call alone on the device after the timed region (k_miller: "
+                        "%d set pairs + %d group pairs = one wave per SIMD), HIP events on the "
+                        "launching stream, median of 2" % (roof["sets"], roof["sets"], ngr),
+            "work_per_set": "%d Fp-mul-eq x %d MAC" % (per_set[dom], MACS_PER_FP_MUL),
+            "sets_per_launch": roof["sets"], "ms_per_launch": rk[dom],
+            "kernel_ms_isolated": rk,
+            "traffic_unit": "HBM bytes per launch (PMC (FETCH_SIZE x 2 + WRITE_SIZE) x 1024)",
+            "algorithmic_bytes": alg_bytes,
+            "hbm_GBps": hbm_gbs, "hbm_frac_of_8TBps": hbm_gbs / 8000 if hbm_gbs else None,
+            "pipeline_frac": pipeline_frac}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -741,6 +800,12 @@ def main():
     ap.add_argument("--nkeys", type=int, default=131072)
     ap.add_argument("--inflight", type=int, default=32,
                     help="batches in flight per GPU (concurrent verify calls, like the reference pool's workers)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other measurement (roofline call, configs 2 / 3 / 5, "
+                         "mainnet-shaped leg, node-shape leg, CPU baseline); the --no-* and --node-shape options "
+                         "below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the verdict codes the last timed step returned as DIR/verdicts.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=8192, help="jobs per pass timed on the host CPU (cpu_baseline)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="minimum host-CPU time of the cpu_baseline sample")
@@ -802,12 +867,14 @@ def main():
         got, _ = step()
         lat1.append(time.perf_counter() - ts)
         assert got == expect, "verdict mismatch"
-    # Steady state: super-batches of B calls with B | gcd(W, K), so the W-th and the
-    # (W+K)-th completions both fall on super-batch boundaries, and a long coalescing window
-    # so every super-batch fills to B calls (restored after the timed region)
+    # Steady state: super-batches of B calls and a long coalescing window so every super-batch
+    # fills to B calls (restored after the timed region); the W-th completion falls on a
+    # super-batch boundary, the (W+K)-th on a period boundary when the period divides K
     ndisp = int(os.environ.get("BGV_DISPATCHERS", "2"))
     bcalls = args.calls_per_batch or super_batch_calls(args.nsets)
-    ncalls = timed_calls(args.steps, bcalls, ndisp)
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be at least 1")
+    ncalls = args.steps
     # the window opens on a super-batch boundary: at least `warmup` calls complete before it,
     # and at least --settle-s seconds of full load (the device's clock settles at its power
     # limit within ~0.3 s; a window inside that boost phase reads up to ~20 % high,
@@ -827,10 +894,14 @@ def main():
     lat = win["latencies"]
     stats = win["stats"]
     kms, launches = ctx.profile(0)
-    roof = roofline_isolated(ctx, native, args.nkeys) if world == 1 or rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "verdicts.npy"), np.asarray(win["last_output"], dtype=np.float32))
+    roof = roofline_isolated(ctx, native, args.nkeys) if args.full and (world == 1 or rank == 0) else None
     block = None
     agg = None
-    extras = world == 1 and not args.no_block_import  # N=1 only, outside the timed region
+    extras = args.full and world == 1 and not args.no_block_import  # N=1 only, outside the timed region
     if extras and args.nkeys >= 16896:
         block = block_import_latency(ctx, native, args.nkeys)
     mainnet = None
@@ -839,9 +910,9 @@ def main():
         # 192 calls (12 super-batches): the leg's retry rounds come in bursts, and a 64-call window
         # read 2.3-3.7 M sets/s for the same library (profiles/r05/uniform/)
         mainnet = mainnet_shaped_throughput(ctx, native, args.nkeys, steps=192, settle_s=args.settle_s)
-    sweep = None if args.no_epoch_sweep else epoch_sweep(ctx, native, barrier, rank, world)
+    sweep = epoch_sweep(ctx, native, barrier, rank, world) if args.full and not args.no_epoch_sweep else None
     shape = None
-    if args.node_shape == "on" or (args.node_shape == "auto" and world > 1):
+    if args.full and (args.node_shape == "on" or (args.node_shape == "auto" and world > 1)):
         # rank 0 alone, while the other ranks wait at the barrier with their devices idle
         if rank == 0:
             devs = node_devices(world, local)
@@ -850,38 +921,9 @@ def main():
 
     if rank == 0:
         total_sets = args.nsets * ncalls * world
-        opc = json.load(open(os.path.join(ROOT, "profiles", "opcounts.json")))["fp_mul_eq"]
-        per_set = {"k_prep": opc["k_sig"] + opc["k_hash"] + opc["k_pk[n_pk=1]"], "k_miller": opc["k_miller"]}
         # timed region: HIP-event time per launch (a kernel's span includes its overlap with
         # the other in-flight super-batches' kernels on other streams)
         avg = {k: v / max(1, launches) for k, v in kms.items()}
-        slots = statistics.mean(s.sets_verified for s in stats)
-        groups = statistics.mean(s.device_groups for s in stats)
-        # whole-pipeline VALU figure: every verify kernel's counted work over the step time
-        per_group = opc["k_final[per group]"] + opc["k_final[group sig pair]"]
-        per_slot_close = opc["k_final[per product step]"] + opc["k_final[per slot sig add]"]
-        pipeline_macs = ((sum(per_set.values()) + per_slot_close) * slots + per_group * groups) \
-            * MACS_PER_FP_MUL * ncalls * world
-        pipeline_frac = pipeline_macs / elapsed / (PEAK_MAC_PER_S * world)
-        # dominant kernel at full occupancy, alone on the device (roofline_isolated): its
-        # algorithmic MACs (set pairs + the group pairs on the same launch) / its HIP-event time
-        rk = roof["kernel_ms"]
-        dom = max(per_set, key=lambda k: rk.get(k, 0))
-        ngr = roof["sets"] // 64
-        work = {"k_miller": roof["sets"] * opc["k_miller"] + ngr * opc["k_final[group sig pair]"],
-                "k_prep": roof["sets"] * per_set["k_prep"]}[dom]
-        achieved = work * MACS_PER_FP_MUL / (rk[dom] * 1e-3)
-        # HBM bytes of that same launch from the committed PMC passes (TRAFFIC_FILE:
-        # (FETCH_SIZE x 2 + WRITE_SIZE) x 1024, rocprofv3 reports KB) and the algorithmic bytes
-        traffic = hbm_gbs = None
-        tf = os.path.join(ROOT, TRAFFIC_FILE)
-        if os.path.exists(tf):
-            rec = json.load(open(tf)).get(dom, {})
-            if rec.get("sets") == roof["sets"]:
-                traffic = rec["bytes_per_launch"]
-                hbm_gbs = traffic / (rk[dom] * 1e-3) / 1e9
-        alg_bytes = {"k_miller": roof["sets"] * (112 + 336 + 672 + 8 + 160) + ngr * (336 + 672),
-                     "k_prep": roof["sets"] * (160 + 4 + 112 * 1 + 336 * 2 + 112 + 8)}[dom]
         line = {
             "metric": "verified signature sets/sec (node) at 8192-set batches",
             "value": total_sets / elapsed,
@@ -905,9 +947,10 @@ def main():
                        "batches_in_flight": max(args.inflight, 3 * bcalls), "calls_per_super_batch": bcalls,
                        "parallelism": "dp%d (independent batches per GPU)" % world},
             "timing": "steady state: calls stream with the given number in flight; the window runs from the "
-                      "%d-th to the %d-th completed call (exactly %d calls inside: the %d requested steps rounded "
-                      "up to whole completion periods of %d dispatchers x %d-call super-batches, the library's "
-                      "default geometry, so both edges fall on batch boundaries; the %d warmup steps are the first "
+                      "%d-th to the %d-th completed call (exactly %d calls inside: the %d requested steps; "
+                      "completions repeat with a period of %d dispatchers x %d-call super-batches, so a step count "
+                      "that is a multiple of the period ends the window on a period boundary; the %d warmup steps "
+                      "are the first "
                       "%d completions, rounded up to whole super-batches and extended to >= %.1f s of full load so "
                       "the window runs at the power-settled clock); %d calls completed in all"
                       % (warm_calls, warm_calls + ncalls, ncalls, args.steps, ndisp, bcalls, args.warmup, warm_calls,
@@ -917,20 +960,20 @@ def main():
             "call_device_ms": statistics.mean(s.device_ms for s in stats),
             "call_wall_ms": statistics.mean(s.wall_ms for s in stats),
             "device_groups_per_step": statistics.mean(s.device_groups for s in stats),
-            "roofline": {"bound": "valu", "kernel": dom, "achieved": achieved / 1e12, "peak": PEAK_MAC_PER_S / 1e12,
-                         "unit": "TMAC/s (u32 mad)", "frac": achieved / PEAK_MAC_PER_S, "traffic": traffic,
-                         "measured": "one %d-set verify call alone on the device after the timed region (k_miller: "
-                                     "%d set pairs + %d group pairs = one wave per SIMD), HIP events on the "
-                                     "launching stream, median of 2" % (roof["sets"], roof["sets"], ngr),
-                         "work_per_set": "%d Fp-mul-eq x %d MAC" % (per_set[dom], MACS_PER_FP_MUL),
-                         "sets_per_launch": roof["sets"], "ms_per_launch": rk[dom],
-                         "kernel_ms_isolated": rk,
-                         "traffic_unit": "HBM bytes per launch (PMC (FETCH_SIZE x 2 + WRITE_SIZE) x 1024)",
-                         "algorithmic_bytes": alg_bytes,
-                         "hbm_GBps": hbm_gbs, "hbm_frac_of_8TBps": hbm_gbs / 8000 if hbm_gbs else None,
-                         "pipeline_frac": pipeline_frac},
             "setup_s": setup_s,
         }
+        if roof is not None:
+            opc = json.load(open(os.path.join(ROOT, "profiles", "opcounts.json")))["fp_mul_eq"]
+            per_set = {"k_prep": opc["k_sig"] + opc["k_hash"] + opc["k_pk[n_pk=1]"], "k_miller": opc["k_miller"]}
+            slots = statistics.mean(s.sets_verified for s in stats)
+            groups = statistics.mean(s.device_groups for s in stats)
+            # whole-pipeline VALU figure: every verify kernel's counted work over the step time
+            per_group = opc["k_final[per group]"] + opc["k_final[group sig pair]"]
+            per_slot_close = opc["k_final[per product step]"] + opc["k_final[per slot sig add]"]
+            pipeline_macs = ((sum(per_set.values()) + per_slot_close) * slots + per_group * groups) \
+                * MACS_PER_FP_MUL * ncalls * world
+            pipeline_frac = pipeline_macs / elapsed / (PEAK_MAC_PER_S * world)
+            line["roofline"] = roofline_record(roof, opc, per_set, pipeline_frac)
         if block is not None:
             line["block_import"] = block
         if agg is not None:
@@ -941,7 +984,7 @@ def main():
             line["epoch_sweep"] = sweep
         if shape is not None:
             line["node_single_process"] = shape
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             cb = cpu_baseline(jobs, key_of, expect, min(args.nsets, args.cpu_sample), args.cpu_seconds)
             line["cpu_baseline"] = cb
             # BASELINE.md publishes no number for this metric, so vs_baseline stays null; the ratio

@@ -1,7 +1,7 @@
 """Pins the CPU oracle (oracle/bls12381.py) to the reference's own known-answer data.
 
-* interop-pubkeys.json: copied verbatim from
-  /root/reference/packages/state-transition/test-cache/interop-pubkeys.json
+* interop-pubkeys.json: copied verbatim from the reference's
+  packages/state-transition/test-cache/interop-pubkeys.json
   (100 compressed G1 pubkeys for sk_i of state-transition/src/util/interop.ts:19-22).
 * deposit-0 signature: beacon-node/test/e2e/interop/genesisState.test.ts:51-55
   (minimal preset, GENESIS_FORK_VERSION 0x00000001; signing root built as in

@@ -1,9 +1,9 @@
 """Index-emitting signature-set producers (lodestar_amd/node/signatureSets.js)
 driven through Node.
 
-* SSZ roots pinned by the reference's own fixture, read in place (CPU only; skipped where
-  /root/reference is absent): the first four mainnet blocks of
-  beacon-node/test/unit/sync/backfill/blocks.json, hash_tree_root(block[i]) ==
+* SSZ roots pinned by the reference's own fixture (CPU only): the first four mainnet blocks of
+  beacon-node/test/unit/sync/backfill/blocks.json, stored verbatim as
+  tests/golden/mainnet_backfill_blocks.json, hash_tree_root(block[i]) ==
   block[i+1].parent_root.
 * Fork digests of mainnet (ForkData roots) against the published values: phase0 b5303f2a,
   altair afcaaba0, bellatrix 4a26c58b (the last also in network/gossip/scoringParameters.ts:178).
@@ -26,7 +26,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = os.path.join(ROOT, "tests", "node", "signature_sets.js")
-MAINNET_BLOCKS = "/root/reference/packages/beacon-node/test/unit/sync/backfill/blocks.json"
+MAINNET_BLOCKS = os.path.join(ROOT, "tests", "golden", "mainnet_backfill_blocks.json")
 R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 MAINNET_GVR = "4b363db94e286120d76eb905340fdd4e54bfe9f06bf33ff6cf5ad27f511bfe95"
 
@@ -164,7 +164,6 @@ def produced(c, tmp_path):
 
 
 # ---- tests ------------------------------------------------------------------------------------
-@pytest.mark.skipif(not os.path.exists(MAINNET_BLOCKS), reason="reference fixture not present")
 def test_mainnet_block_roots_chain():
     blocks = json.load(open(MAINNET_BLOCKS))
     got = json.loads(node("roots", MAINNET_BLOCKS))

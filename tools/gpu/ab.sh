@@ -11,7 +11,7 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc
 for i in $(seq 1 "$N"); do
   for L in "$@"; do
     tag=$(basename "$L" .so)
-    BLSGPU_LIB=$L timeout -k 10 150 python bench.py --no-cpu-baseline --no-block-import --no-epoch-sweep \
+    BLSGPU_LIB=$L timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-block-import --no-epoch-sweep \
       >> "$OUT/ab_$tag.jsonl" 2>> "$OUT/ab.err" || { echo "bench $tag rc=$?: stopping"; exit 1; }
   done
 done

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 for i in $(seq 1 "$N"); do
   for spec in "$@"; do
     IFS='|' read -r tag envs args <<< "$spec"
-    env $envs timeout -k 10 150 python bench.py --no-cpu-baseline --no-block-import --no-epoch-sweep $args \
+    env $envs timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-block-import --no-epoch-sweep $args \
       >> "$O/ab_$tag.jsonl" 2>> "$O/ab_$tag.err" || { echo "bench $tag rc=$?: stopping"; exit 1; }
     tail -1 "$O/ab_$tag.jsonl" | python tools/gpu/summarize.py - | sed "s/^-/$tag/"
   done

@@ -4,7 +4,7 @@
 # Steps, run in the order given; the first failing GPU step ends the session (no retries):
 #   suite    pytest -m gpu (thread timeouts, one process)
 #   smoke    __graft_entry__.smoke()
-#   bench    python bench.py (the default command the driver runs)  -> OUTDIR/bench_default.json
+#   bench    python bench.py --full (every measurement of the bench)   -> OUTDIR/bench_default.json
 #   quick    bench headline window only (no CPU baseline, no extras) -> OUTDIR/bench_quick.jsonl (appends)
 #   driver   the headline window with the driver's step counts (--steps 20 --warmup 5) and with
 #            the default ones (64 / 16), back to back                 -> OUTDIR/bench_steps.jsonl (appends)
@@ -33,31 +33,31 @@ for step in "$@"; do
         || fail smoke $? "$O/smoke.txt"
       tail -1 "$O/smoke.txt" ;;
     bench)
-      timeout -k 10 300 python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err" \
+      timeout -k 10 300 python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err" \
         || fail bench $? "$O/bench_default.err"
       python tools/gpu/summarize.py "$O/bench_default.json" ;;
     quick)
-      timeout -k 10 150 python bench.py --no-cpu-baseline --no-block-import --no-epoch-sweep \
+      timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-block-import --no-epoch-sweep \
         >> "$O/bench_quick.jsonl" 2>> "$O/bench_quick.err" || fail quick $? "$O/bench_quick.err"
       tail -1 "$O/bench_quick.jsonl" | python tools/gpu/summarize.py - ;;
     driver)
       for sw in "20 5" "64 16"; do
         read -r ks kw <<< "$sw"
-        timeout -k 10 150 python bench.py --steps $ks --warmup $kw --no-cpu-baseline --no-block-import --no-epoch-sweep \
+        timeout -k 10 150 python bench.py --full --steps $ks --warmup $kw --no-cpu-baseline --no-block-import --no-epoch-sweep \
           >> "$O/bench_steps.jsonl" 2>> "$O/bench_steps.err" || fail driver $? "$O/bench_steps.err"
       done
       tail -2 "$O/bench_steps.jsonl" | python tools/gpu/summarize.py - ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/bench_trace" -o run --output-format csv \
-        -- python3 bench.py --no-cpu-baseline > "$O/bench_traced.json" 2> "$O/bench_traced.err" \
+        -- python3 bench.py --full --no-cpu-baseline > "$O/bench_traced.json" 2> "$O/bench_traced.err" \
         || fail trace $? "$O/bench_traced.err" ;;
     retrytrace)
       for c in 1 0; do
         timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$O/retry_c$c" -o run --output-format csv \
-          -- python3 bench.py --no-cpu-baseline --no-block-import --no-epoch-sweep --corrupt 0.0$c \
+          -- python3 bench.py --full --no-cpu-baseline --no-block-import --no-epoch-sweep --corrupt 0.0$c \
           > "$O/retry_c$c.json" 2> "$O/retry_c$c.err" || fail retrytrace $? "$O/retry_c$c.err"
       done
-      BGV_TRACE=1 timeout -k 10 150 python bench.py --no-cpu-baseline --no-block-import --no-epoch-sweep \
+      BGV_TRACE=1 timeout -k 10 150 python bench.py --full --no-cpu-baseline --no-block-import --no-epoch-sweep \
         > "$O/retry_trace.json" 2> "$O/retry_trace.err" || fail retrytrace $? "$O/retry_trace.err"
       cat "$O"/retry_c*.json | python tools/gpu/summarize.py - ;;
     roof)
