@@ -189,7 +189,7 @@ int bgv_final_verify(bgv_ctx* ctx, const uint8_t* partials, size_t n, int32_t* o
 int bgv_debug_prepare(bgv_ctx* ctx, const bgv_set* sets, size_t nsets, int path, uint64_t seed, uint8_t* out_h192,
                       uint8_t* out_f576, int32_t* out_status);
 
-/* Parity hook for uniform groups (tests only; bgv_api.cpp call_submit / call_build_parts).
+/* Parity hook for uniform groups (tests only; bgv_host_layout.h layout_call / bgv_retry_plan.h build_parts).
  * The n sets (2..64, cached pubkeys, one signing root, 96-B signatures) form ONE uniform
  * first-pass group of a bulk batch, randomizers as bgv_debug_prepare's; then ntests retry tests
  * over its slots, each a slot mask (bit k = set k), weighted (slot k with weight k + 1,

@@ -40,41 +40,16 @@
 
 #include "../../include/blsgpu.h"
 #include "bgv_launch.h"
+#include "bgv_retry_plan.h"  // with bgv_host_layout.h: the host-only layout and retry planning
 #include "bls_field.h"  // fp12_t (sizes of the per-group u copies)
 
-// parts a failing mixed group is split into per retry round (BGV_RETRY_FANOUT env).
-// Group closings are team-parallel and cheap in latency, so bisecting (64 -> 8 -> 1)
-// costs an extra round but ~4x fewer final exponentiations than going per job at once.
-#define BGV_RETRY_FANOUT 8
 // slots merged into one device super-batch (BGV_MAX_BATCH_SLOTS env)
 #define BGV_MAX_BATCH_SLOTS 131072
 // dispatcher threads (= HIP streams) per device (BGV_DISPATCHERS env)
 #define BGV_DISPATCHERS 2
 
-static size_t env_size(const char* name, size_t dflt, size_t lo) {
-  const char* e = getenv(name);
-  long n = e ? atol(e) : 0;
-  return n >= (long)lo ? (size_t)n : dflt;
-}
-static size_t retry_fanout() {
-  static const size_t v = env_size("BGV_RETRY_FANOUT", BGV_RETRY_FANOUT, 2);
-  return v;
-}
 static size_t max_batch_slots() {
   static const size_t v = env_size("BGV_MAX_BATCH_SLOTS", BGV_MAX_BATCH_SLOTS, BGV_WAVE);
-  return v;
-}
-// sets per first-pass device group, a power of two <= 64 (BGV_GROUP_SLOTS env).
-// Smaller groups fail less often under invalid signatures (fewer retried jobs)
-// at the price of more final exponentiations when every set is valid.
-#define BGV_GROUP_SLOTS 64
-static uint32_t group_slots() {
-  static const uint32_t v = [] {
-    size_t n = env_size("BGV_GROUP_SLOTS", BGV_GROUP_SLOTS, 1);
-    uint32_t p = 1;
-    while (p * 2 <= n && p * 2 <= BGV_WAVE) p *= 2;
-    return p;
-  }();
   return v;
 }
 // how long an idle dispatcher waits for more calls to merge (BGV_COALESCE_US env)
@@ -109,28 +84,6 @@ static int execs_per_device() {
   static const int v = (int)env_size("BGV_EXECS", 2 * BGV_DISPATCHERS, 1);
   return std::max(v, dispatchers_per_device());
 }
-
-// BGV_UNIFORM=0 turns off uniform groups (BGV_GROUP_UNIFORM: one Miller loop per group whose sets
-// share a signing root, and the grouping of a call's batchable one-set jobs by root that makes
-// them), for A/B measurements; on by default
-static bool uniform_enabled() {
-  static const bool v = [] {
-    const char* e = getenv("BGV_UNIFORM");
-    return !(e && atoi(e) == 0);
-  }();
-  return v;
-}
-// BGV_WEIGHTED_UNIFORM=0: failing uniform groups take the pattern tests at once (no weighted
-// test first; call_build_parts), for A/B measurements
-static bool weighted_uniform_enabled() {
-  static const bool v = [] {
-    const char* e = getenv("BGV_WEIGHTED_UNIFORM");
-    return !(e && atoi(e) == 0);
-  }();
-  return v;
-}
-// calls with fewer batchable one-set jobs take the latency path: their jobs keep their order
-#define BGV_UNIFORM_MIN_JOBS 1024
 
 // Retry threads per device (BGV_RETRY_THREADS), each with its own high-priority stream: the
 // retry rounds of several super-batches then run side by side instead of queueing behind one
@@ -272,208 +225,24 @@ struct Device {
   std::unique_ptr<std::mutex> compute_mu = std::make_unique<std::mutex>();
 };
 
-// An allocator whose value-less construct leaves the element uninitialized: resizing a vector of
-// slot records then writes nothing (layout_one_job_fast fills every record itself)
-template <class T>
-struct uninit_alloc : std::allocator<T> {
-  template <class U>
-  struct rebind {
-    using other = uninit_alloc<U>;
-  };
-  uninit_alloc() = default;
-  template <class U>
-  uninit_alloc(const uninit_alloc<U>&) {}
-  template <class U>
-  void construct(U* p) noexcept {
-    ::new (static_cast<void*>(p)) U;
-  }
-  template <class U, class... A>
-  void construct(U* p, A&&... a) {
-    ::new (static_cast<void*>(p)) U(std::forward<A>(a)...);
-  }
-};
-
-// jobs -> slots/groups of one call
-struct Layout {
-  std::vector<bgv_dslot, uninit_alloc<bgv_dslot>> slots;
-  std::vector<bgv_dgroup> groups;
-  std::vector<int32_t> slot_set;  // set index per slot (-1 = pad)
-  std::vector<std::vector<uint32_t>> job_groups;
-  std::vector<uint32_t> job_first_slot;  // first slot of each laid-out job (its slots are contiguous)
-  std::vector<char> group_shared;        // group holds sets of more than one job
-  std::vector<char> group_uniform;       // every set of the group shares one signing root and no
-                                         // batchable job in it spans groups (BGV_GROUP_UNIFORM in bulk
-                                         // batches)
-  std::vector<uint32_t> idx;             // concatenated pubkey indices
-  std::vector<uint8_t> pkb;              // concatenated 96-B pubkey records
-  std::vector<uint32_t> uniq;            // first slot of each distinct signing root (hash_to_G2 once)
-};
-
-struct Builder {
-  Layout& L;
-  bool open = false;  // a group is open for appending
-  uint32_t open_group = 0;
-  int open_job = -1;
-  // signing root -> its first slot, keyed by the root's first 8 bytes (a SHA-256 output); a
-  // key collision between different roots only costs one extra hash
-  std::unordered_map<uint64_t, uint32_t> first_root;
-  explicit Builder(Layout& l) : L(l) {}
-
-  void close_group() { open = false; }
-  void new_group() {
-    // start at the next wave boundary
-    uint32_t first = (uint32_t)L.slots.size();
-    const uint32_t gs = group_slots();
-    uint32_t aligned = (first + gs - 1) / gs * gs;
-    while (L.slots.size() < aligned) pad();
-    L.groups.push_back(bgv_dgroup{aligned, 0, BGV_ALL_SLOTS});
-    L.group_shared.push_back(0);
-    L.group_uniform.push_back(1);
-    open_group = (uint32_t)L.groups.size() - 1;
-    open = true;
-    open_job = -1;
-  }
-  void pad() {
-    bgv_dslot s;
-    memset(&s, 0, sizeof(s));
-    s.flags = BGV_SLOT_PAD;
-    s.hsrc = (uint32_t)L.slots.size();
-    L.slots.push_back(s);
-    L.slot_set.push_back(-1);
-  }
-  void pad_to_wave() {
-    while (L.slots.size() % BGV_WAVE) pad();
-  }
-  void add(int job, uint32_t set_index, const bgv_set& st, bool first_of_job) {
-    if (!open || L.groups[open_group].n_slots == group_slots()) new_group();
-    bgv_dgroup& g = L.groups[open_group];
-    if (open_job >= 0 && open_job != job) L.group_shared[open_group] = 1;
-    open_job = job;
-    std::vector<uint32_t>& jg = L.job_groups[job];
-    if (jg.empty() || jg.back() != open_group) jg.push_back(open_group);
-    if (first_of_job) L.job_first_slot[job] = (uint32_t)L.slots.size();
-    bgv_dslot s;
-    memset(&s, 0, sizeof(s));
-    s.n_pk = st.n_pk;
-    s.sig_len = st.sig_len;
-    s.group = open_group;
-    if (st.pk_indices) {
-      s.flags = BGV_SLOT_PK_CACHED;
-      s.pk_off = (uint32_t)L.idx.size();
-      L.idx.insert(L.idx.end(), st.pk_indices, st.pk_indices + st.n_pk);
-    } else {
-      s.flags = BGV_SLOT_PK_BYTES;
-      s.pk_off = (uint32_t)(L.pkb.size() / 96);
-      L.pkb.insert(L.pkb.end(), st.pk_bytes, st.pk_bytes + 96ull * st.n_pk);
-    }
-    memcpy(s.msg, st.msg, 32);
-    if (st.sig_len == 96) memcpy(s.sig, st.sig, 96);
-    const uint32_t self = (uint32_t)L.slots.size();
-    if (self > 0 && !(L.slots[self - 1].flags & BGV_SLOT_PAD) && memcmp(L.slots[self - 1].msg, st.msg, 32) == 0) {
-      s.hsrc = L.slots[self - 1].hsrc;  // the previous slot's root (committees arrive together)
-    } else {
-      uint64_t key;
-      memcpy(&key, st.msg, 8);
-      auto it = first_root.find(key);
-      if (it == first_root.end()) it = first_root.emplace(key, self).first;
-      if (it->second != self && memcmp(L.slots[it->second].msg, st.msg, 32) == 0) {
-        s.hsrc = it->second;  // same root as an earlier slot of this call
-      } else {
-        s.hsrc = self;
-        L.uniq.push_back(self);
-      }
-    }
-    if (g.n_slots > 0 && L.slots[g.first_slot].hsrc != s.hsrc) L.group_uniform[open_group] = 0;
-    L.slots.push_back(s);
-    L.slot_set.push_back((int32_t)set_index);
-    g.n_slots++;
-  }
-};
-
-struct Part {  // one retry test: consecutive jobs of one failing unit, and the device groups covering them
-  std::vector<size_t> jobs;
-  std::vector<uint32_t> groups;  // indices into the round's merged group list
-  int pattern = -1;              // pattern test: index into Call::punits (its bit is the part's order)
-};
-
-// A failing first-pass group whose jobs all lie inside it (gossip: one-set jobs) is retried
-// by pattern tests in ONE round: test S_j = the jobs whose index in the group has bit j set,
-// j < ceil(log2 n).  The complement's verdict comes for free: the group's pairing value is
-// the product of S_j's and its complement's, so with u = gprod^((p^2+1) 3 (p^4-p^2+1)/r) (the
-// pairing value is conj(u)/u, bls_team.h tm_final_exp_u) the complement passes iff
-// u_group * conj(u_j) lies in Fp6.  A job inside any passing set is valid; every invalid
-// job lies in no passing set, so one remaining candidate is the invalid job, and two or
-// more go to the next round (usually as singletons).  k tests per failing group instead of
-// fanout-bisection's 8 + 8 over two rounds.
-//
-// The remaining candidates (two or more invalid jobs: 2^h of them for two jobs whose indices
-// differ in h bits) are tested one job per device group in the next round, so a failing
-// group is resolved in at most two rounds: a round costs about the same latency whether it
-// tests hundreds or thousands of groups, while a second pattern round over the candidates
-// need not shrink them (two invalid jobs at the first and last candidate index).
-//
-// Two invalid jobs i, j (the usual case of a second round) leave as candidates the 2^h jobs
-// that agree with both where i and j agree, h = the number of bits D where S_b and its
-// complement both failed; the candidates pair up as x, x ^ D.  The next round tests the pairs
-// (2^(h-1) tests instead of 2^h single jobs): when exactly one test fails and it is a pair,
-// both its jobs are invalid (for b in D, S_b and its complement each hold an invalid job, and
-// every invalid job is a candidate of that one pair); a failing single job is invalid; jobs of
-// a failing pair next to other failures are tested alone in one more round.
-struct PatternUnit {
-  uint32_t group = 0;              // the call's first-pass group
-  int kind = 0;                    // 0: pattern tests S_j; 1: pairs and single jobs; 2: one weighted test
-  std::vector<size_t> jobs;        // kind 0: its jobs in slot order
-  std::vector<uint32_t> tests;     // round group index of each test
-  std::vector<std::vector<size_t>> test_jobs;  // kind 1: each test's jobs
-};
-// units from the first pass of at most this many jobs (not pattern-testable) are tested one
-// job per device group
-static const size_t kSingletonMax = 8;
-// a signing root with at least this many one-set jobs starts its own device group (call_submit)
-#ifndef BGV_UNIFORM_ALIGN_MIN
-#define BGV_UNIFORM_ALIGN_MIN 32  // A/B: a huge value keeps the round-5 layout (roots back to back)
-#endif
-static const size_t kUniformAlignMin = BGV_UNIFORM_ALIGN_MIN;
-
-// One bgv_verify call travelling through a dispatcher.
-struct Call {
-  const bgv_job* jobs = nullptr;
-  size_t njobs = 0;
+// One bgv_verify call travelling through a dispatcher: its host state (layout, codes, retry
+// units: CallPlan, bgv_retry_plan.h) and how its caller hears of the end.
+struct Call : CallPlan {
   const bgv_set* sets = nullptr;
-  size_t nsets = 0;
-  int mode = 0;
   int32_t* out = nullptr;
   bgv_stats* stats_out = nullptr;
   bgv_done_fn done = nullptr;
   void* user = nullptr;
   bool owned = false;
   std::chrono::steady_clock::time_point t0;
-  // host state
-  Layout L;
-  std::vector<int32_t> code;  // 2 = pending
-  std::vector<size_t> todo;
-  std::vector<int32_t> set_sig, set_pk;
-  std::vector<std::vector<size_t>> units;  // pending retry units
-  std::vector<int> unit_group;             // first-pass group the unit's jobs lie in (-1: not known)
-  std::vector<int> unit_rounds;            // pattern rounds the unit's jobs have been through
-  std::vector<std::vector<uint32_t>> unit_idx;  // after a pattern round: the candidates' pattern indices
-  std::vector<uint32_t> unit_dmask;        // ... and the index bits D of their pairing (0: none)
-  std::vector<Part> parts;
-  std::vector<PatternUnit> punits;         // this round's pattern-tested units
-  bgv_stats st{};
-  // bgv_verify_partial: the call's Miller-loop product (576 B) and its two status codes
-  uint8_t* partial_out = nullptr;
-  int32_t* partial_codes = nullptr;
   int dev = -1;  // index in bgv_ctx::devs of the only device whose dispatchers may take it (-1: any)
   bgv_job pjob{};
   int32_t pcode = 0;
-  uint32_t slot_base = 0;  // offset of this call's slots in the merged batch
   int rc = BGV_OK;
   // completion
   std::mutex mu;
   std::condition_variable cv;
   bool finished = false;
-  bool shared_job(size_t j) const { return mode == BGV_MODE_WORKER && jobs[j].batchable; }
 };
 
 }  // namespace
@@ -536,22 +305,6 @@ static uint64_t splitmix64(uint64_t* s) {
 }
 
 // nonzero 64-bit randomizers (blst mul_n_aggregate with 64 random bits)
-// fn(lo, hi) over [0, n) in up to 8 host threads when n is large (a 2^20-set call: the
-// merge's 168 MB of slot records and 8 MB of getrandom output), else inline
-template <class F>
-static void par_ranges(size_t n, F fn) {
-  const size_t kMin = size_t(1) << 17;
-  const unsigned nt = n >= kMin ? std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-  if (nt <= 1) {
-    fn(size_t(0), n);
-    return;
-  }
-  std::vector<std::thread> th;
-  for (unsigned t = 1; t < nt; ++t) th.emplace_back(fn, n * t / nt, n * (t + 1) / nt);
-  fn(size_t(0), n / nt);
-  for (auto& t : th) t.join();
-}
-
 static void fill_scalars(bgv_ctx* c, uint64_t* out, size_t n) {
   {
     std::lock_guard<std::mutex> lk(c->rng_mu);
@@ -703,24 +456,6 @@ static bgv_dev_batch make_batch(Device& d, Exec& x, uint32_t nslots, uint32_t ng
   return b;
 }
 
-// Outcome of one job from its slots' statuses (maybeBatch.ts:16-39 + blst semantics):
-//   any undecodable / not-in-group signature -> error of the first such set (fromBytes throws)
-//   any infinity public key                  -> 1 set: false (core verify), >= 2 sets: BLST_PK_IS_INFINITY
-// returns 2 when the verdict depends on the groups.
-static int32_t job_precheck(const std::vector<int32_t>& set_sig, const std::vector<int32_t>& set_pk,
-                            const bgv_job& j) {
-  for (uint32_t k = 0; k < j.n_sets; ++k) {
-    const int32_t s = set_sig[j.first_set + k];
-    if (s != BGV_OK && s != BGV_ST_INFINITY) return -s;
-  }
-  for (uint32_t k = 0; k < j.n_sets; ++k) {
-    const int32_t p = set_pk[j.first_set + k];
-    if (p == BGV_ST_INFINITY) return j.n_sets >= 2 ? -BGV_BLST_PK_IS_INFINITY : 0;
-    if (p != BGV_OK) return -p;  // undecodable uncompressed pubkey record
-  }
-  return 2;
-}
-
 // ---------------------------------------------------------------------------
 // Call lifecycle
 // ---------------------------------------------------------------------------
@@ -774,85 +509,6 @@ static int host_job_code(const bgv_ctx* c, const bgv_job& jb, const bgv_set* set
   return BGV_OK;
 }
 
-// The layout Builder makes for a call of ONE non-batchable job of cached-key sets (slots in set
-// order from slot 0, groups of group_slots() consecutive slots, pads to the wave boundary),
-// with the per-slot records filled by several host threads: the config-5 sweep's 2^20-set
-// job took ~50 ms on one thread.  false: not such a call (the Builder lays it out).
-static bool layout_one_job_fast(Call* call, const bgv_job& jb, const bgv_set* sets) {
-  const uint32_t n = jb.n_sets, gs = group_slots();
-  const bgv_set* S = sets + jb.first_set;
-  if (n < (1u << 17)) return false;
-  for (uint32_t i = 0; i < n; ++i)
-    if (!S[i].pk_indices) return false;
-  Layout& L = call->L;
-  // signing roots in order: the previous set's root, else the first set with the same root (a
-  // key collision between different roots opens a root of its own), as Builder::add
-  std::vector<uint32_t> hsrc(n), pk_off(n);
-  std::unordered_map<uint64_t, uint32_t> first_root;
-  uint32_t npk = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    pk_off[i] = npk;
-    npk += S[i].n_pk;
-    if (i > 0 && memcmp(S[i - 1].msg, S[i].msg, 32) == 0) {
-      hsrc[i] = hsrc[i - 1];
-      continue;
-    }
-    uint64_t key;
-    memcpy(&key, S[i].msg, 8);
-    auto it = first_root.find(key);
-    if (it == first_root.end()) it = first_root.emplace(key, i).first;
-    if (it->second != i && memcmp(S[it->second].msg, S[i].msg, 32) == 0) {
-      hsrc[i] = it->second;
-    } else {
-      hsrc[i] = i;
-      L.uniq.push_back(i);
-    }
-  }
-  const uint32_t nslots = (n + BGV_WAVE - 1) / BGV_WAVE * BGV_WAVE, ng = (n + gs - 1) / gs;
-  L.slots.resize(nslots);
-  L.slot_set.resize(nslots);
-  L.idx.resize(npk);
-  par_ranges(nslots, [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; ++i) {
-      bgv_dslot& s = L.slots[i];
-      memset(&s, 0, sizeof(s));
-      if (i >= n) {
-        s.flags = BGV_SLOT_PAD;
-        s.hsrc = (uint32_t)i;
-        L.slot_set[i] = -1;
-        continue;
-      }
-      const bgv_set& st = S[i];
-      s.n_pk = st.n_pk;
-      s.sig_len = st.sig_len;
-      s.group = (uint32_t)(i / gs);
-      s.flags = BGV_SLOT_PK_CACHED;
-      s.pk_off = pk_off[i];
-      memcpy(L.idx.data() + pk_off[i], st.pk_indices, 4ull * st.n_pk);
-      memcpy(s.msg, st.msg, 32);
-      if (st.sig_len == 96) memcpy(s.sig, st.sig, 96);
-      s.hsrc = hsrc[i];
-      L.slot_set[i] = (int32_t)(jb.first_set + i);
-    }
-  });
-  L.groups.resize(ng);
-  L.group_shared.assign(ng, 0);
-  L.group_uniform.assign(ng, 1);
-  for (uint32_t g = 0; g < ng; ++g) {
-    const uint32_t f = g * gs, m = std::min(gs, n - f);
-    L.groups[g] = bgv_dgroup{f, m, BGV_ALL_SLOTS};
-    for (uint32_t k = 1; k < m; ++k)
-      if (hsrc[f + k] != hsrc[f]) {
-        L.group_uniform[g] = 0;
-        break;
-      }
-  }
-  L.job_groups[0].resize(ng);
-  for (uint32_t g = 0; g < ng; ++g) L.job_groups[0][g] = g;
-  L.job_first_slot[0] = 0;
-  return true;
-}
-
 // A freshly allocated layout of a huge call is first touched page by page: 168 MB of slot
 // records for a 2^20-set call are ~43,000 page faults.  Transparent huge pages (where the host
 // allows them) cut that to ~100.
@@ -887,10 +543,8 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
       if (host_job_code(c, jobs[j], sets, &call->code[j]) != BGV_OK) return -BGV_E_ARG;
     }
   }
-  // pass-1 layout: non-batchable jobs own their groups; batchable jobs (worker mode) share
+  // pass-1 layout (bgv_host_layout.h)
   Layout& L = call->L;
-  L.job_groups.resize(njobs);
-  L.job_first_slot.assign(njobs, 0);
   {
     size_t npk = 0;
     for (size_t i = 0; i < nsets; ++i)
@@ -905,91 +559,7 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
       advise_huge(L.idx.data(), 4 * npk);
     }
   }
-  Builder B(L);
-  for (size_t j = 0; j < njobs; ++j)
-    if (call->code[j] == 2) call->todo.push_back(j);
-  const bool fast = njobs == 1 && call->todo.size() == 1 && !call->shared_job(0) &&
-                    layout_one_job_fast(call, jobs[0], sets);
-  for (size_t j : call->todo) {
-    if (call->shared_job(j) || fast) continue;
-    B.close_group();
-    for (uint32_t k = 0; k < jobs[j].n_sets; ++k)
-      B.add((int)j, jobs[j].first_set + k, sets[jobs[j].first_set + k], k == 0);
-    B.close_group();
-  }
-  B.close_group();
-  // Batchable jobs share groups in any order (verdicts map by job).  One-set jobs go grouped by
-  // signing root -- the roots in order of first appearance, each root's jobs in call order -- so
-  // that the sets of a root fill whole groups (BGV_GROUP_UNIFORM: one Miller loop for the group;
-  // gossip attestations of one committee share a root); then multi-set jobs.
-  std::vector<size_t> shared_order;
-  std::vector<size_t> breaks;  // positions in shared_order where a new device group starts
-  size_t n_one = 0;
-  for (size_t j : call->todo)
-    if (call->shared_job(j) && jobs[j].n_sets == 1) ++n_one;
-  if (uniform_enabled() && n_one >= BGV_UNIFORM_MIN_JOBS) {
-    std::unordered_map<uint64_t, uint32_t> bucket_of;
-    bucket_of.reserve(2 * n_one);
-    std::vector<std::vector<size_t>> buckets;
-    std::vector<const uint8_t*> broot;
-    bool grouped = false;  // some root recurs after another root: the order changes
-    uint32_t last = UINT32_MAX;
-    for (size_t j : call->todo) {
-      if (!call->shared_job(j) || jobs[j].n_sets != 1) continue;
-      const uint8_t* m = sets[jobs[j].first_set].msg;
-      uint64_t key;
-      memcpy(&key, m, 8);
-      auto it = bucket_of.find(key);
-      uint32_t b;
-      if (it != bucket_of.end() && memcmp(broot[it->second], m, 32) == 0) {
-        b = it->second;
-      } else {  // a new root (a key collision between different roots just opens another bucket)
-        b = (uint32_t)buckets.size();
-        buckets.emplace_back();
-        broot.push_back(m);
-        if (it == bucket_of.end()) bucket_of.emplace(key, b);
-      }
-      grouped = grouped || (b != last && !buckets[b].empty());
-      last = b;
-      buckets[b].push_back(j);
-    }
-    if (grouped) {
-      // A root with at least half a group of jobs starts a group of its own, so its groups stay
-      // uniform whatever the roots before it held (a committee one set short -- a corrupted
-      // message, a late attestation -- would otherwise shift every later root across a group
-      // boundary: both groups mixed, per-slot Miller loops, pattern tests instead of the weighted
-      // one); the roots with fewer jobs share mixed groups after them, in order of appearance.
-      for (const auto& bk : buckets)
-        if (bk.size() >= kUniformAlignMin) {
-          breaks.push_back(shared_order.size());
-          shared_order.insert(shared_order.end(), bk.begin(), bk.end());
-        }
-      breaks.push_back(shared_order.size());
-      for (const auto& bk : buckets)
-        if (bk.size() < kUniformAlignMin) shared_order.insert(shared_order.end(), bk.begin(), bk.end());
-      for (size_t j : call->todo)
-        if (call->shared_job(j) && jobs[j].n_sets != 1) shared_order.push_back(j);
-    }
-  }
-  if (shared_order.empty())  // call order
-    for (size_t j : call->todo)
-      if (call->shared_job(j)) shared_order.push_back(j);
-  size_t bi = 0;
-  for (size_t q = 0; q < shared_order.size(); ++q) {
-    if (bi < breaks.size() && breaks[bi] == q) B.close_group();
-    while (bi < breaks.size() && breaks[bi] <= q) ++bi;
-    const size_t j = shared_order[q];
-    for (uint32_t k = 0; k < jobs[j].n_sets; ++k)
-      B.add((int)j, jobs[j].first_set + k, sets[jobs[j].first_set + k], k == 0);
-  }
-  B.pad_to_wave();
-  // A batchable job over several groups may be retried by fanout over its slots, which needs
-  // their own pairs: its groups are not uniform.  A non-batchable job is never retried (its
-  // verdict is its groups' AND, call_after_pass1), so its groups stay uniform where their sets
-  // share a root: the config-5 sweep's one 2^20-set job, committee by committee.
-  for (size_t j : call->todo)
-    if (L.job_groups[j].size() > 1 && call->shared_job(j))
-      for (uint32_t g : L.job_groups[j]) L.group_uniform[g] = 0;
+  layout_call(L, call->todo, jobs, njobs, sets, mode, call->code);
   call->set_sig.assign(nsets, 0);
   call->set_pk.assign(nsets, 0);
   if (L.slots.empty()) {  // nothing for the device
@@ -1008,392 +578,10 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
   return BGV_OK;
 }
 
-// After pass 1: statuses, verdicts and the retry units of one call.
-static void call_after_pass1(Call* call, const int32_t* ss, const int32_t* ps, const int32_t* verdict) {
-  Layout& L = call->L;
-  const uint32_t nslots = (uint32_t)L.slots.size(), ngroups = (uint32_t)L.groups.size();
-  for (uint32_t i = 0; i < nslots; ++i)
-    if (L.slot_set[i] >= 0) {
-      call->set_sig[L.slot_set[i]] = ss[i];
-      call->set_pk[L.slot_set[i]] = ps[i];
-      call->st.sets_verified++;
-    }
-  call->st.device_groups += ngroups;
-  if (call->partial_out) {
-    // first signature error and first pubkey condition in set order (the caller combines
-    // the shards' codes in rank order, as job_precheck does within one job)
-    int32_t sig = 0, pk = 0;
-    for (size_t i = 0; i < call->nsets; ++i) {
-      const int32_t a = call->set_sig[i], q = call->set_pk[i];
-      if (!sig && a != BGV_OK && a != BGV_ST_INFINITY) sig = -a;
-      if (!pk && q == BGV_ST_INFINITY) pk = 1;
-      if (!pk && q != BGV_OK && q != BGV_ST_INFINITY) pk = -q;
-    }
-    call->partial_codes[0] = sig;
-    call->partial_codes[1] = pk;
-    for (size_t j : call->todo) call->code[j] = 1;
-    return;
-  }
-  std::vector<char> group_retried(ngroups, 0);
-  std::vector<int> unit_of_group(ngroups, -1);
-  std::vector<char> seen(call->njobs, 0);
-  for (size_t j : call->todo) {
-    const int32_t pre = job_precheck(call->set_sig, call->set_pk, call->jobs[j]);
-    if (pre != 2) {
-      call->code[j] = pre;
-      continue;
-    }
-    bool ok = true;
-    int first_bad_shared = -1;
-    for (uint32_t g : L.job_groups[j])
-      if (!(verdict[g] & 1)) {
-        ok = false;
-        if (L.group_shared[g] && first_bad_shared < 0) first_bad_shared = (int)g;
-      }
-    if (first_bad_shared >= 0) {
-      group_retried[first_bad_shared] = 1;
-      if (unit_of_group[first_bad_shared] < 0) {
-        unit_of_group[first_bad_shared] = (int)call->units.size();
-        call->units.emplace_back();
-        call->unit_group.push_back(first_bad_shared);
-        call->unit_rounds.push_back(0);
-        call->unit_idx.emplace_back();
-        call->unit_dmask.push_back(0);
-      }
-      if (!seen[j]) {
-        seen[j] = 1;
-        call->units[unit_of_group[first_bad_shared]].push_back(j);
-      }
-    } else {
-      call->code[j] = ok ? 1 : 0;
-      if (ok && call->shared_job(j)) call->st.batch_sigs_success += call->jobs[j].n_sets;
-    }
-  }
-  for (char r : group_retried) call->st.batch_retries += r;
-}
-
-// A unit from pass 1 is pattern-testable when its jobs lie only in its group and cover every
-// slot of the group that takes part in the group's product (the others -- sets of jobs that
-// failed their precheck -- contribute 1): then a test S_j and its complement partition the
-// group's product.
-static bool pattern_eligible(const Call* call, size_t u) {
-  if (u >= call->unit_group.size() || call->unit_group[u] < 0) return false;
-  const std::vector<size_t>& jobs = call->units[u];
-  if (jobs.size() < 2) return false;
-  const uint32_t g = (uint32_t)call->unit_group[u];
-  const bgv_dgroup& G = call->L.groups[g];
-  uint64_t covered = 0;
-  for (size_t j : jobs) {
-    const auto& jg = call->L.job_groups[j];
-    if (jg.size() != 1 || jg[0] != g) return false;
-    const uint32_t off = call->L.job_first_slot[j] - G.first_slot, n = call->jobs[j].n_sets;
-    covered |= (n >= 64 ? ~0ull : ((1ull << n) - 1)) << off;
-  }
-  for (uint32_t k = 0; k < G.n_slots; ++k) {
-    if ((covered >> k) & 1) continue;
-    const int32_t si = call->L.slot_set[G.first_slot + k];
-    if (si < 0) continue;
-    const int32_t a = call->set_sig[si], q = call->set_pk[si];
-    if ((a == BGV_OK || a == BGV_ST_INFINITY) && q == BGV_OK) return false;  // live, outside the unit
-  }
-  return true;
-}
-
-// A job's slots within its (single) group g, as a device-group mask
-static uint64_t job_mask(const Call* call, size_t j, const bgv_dgroup& g) {
-  const uint32_t off = call->L.job_first_slot[j] - g.first_slot, n = call->jobs[j].n_sets;
-  return (n >= 64 ? ~0ull : ((1ull << n) - 1)) << off;
-}
-
-// every job of the unit lies in the call's group g alone
-static bool unit_in_group(const Call* call, const std::vector<size_t>& jobs, int g) {
-  if (g < 0) return false;
-  for (size_t j : jobs) {
-    const auto& jg = call->L.job_groups[j];
-    if (jg.size() != 1 || jg[0] != (uint32_t)g) return false;
-  }
-  return true;
-}
-
-// Group testing for one retry round: split every pending unit into parts.  gb: the call's
-// first group in the batch when the first pass's u values are on the device (pattern tests
-// possible), else -1.
-static void call_build_parts(Call* call, std::vector<bgv_dgroup>& rg, int64_t gb, bool uniform) {
-  // A test inside a uniform first-pass group (whose slots have no own pair f_i) pairs the sum
-  // of its slots' r_i pk_i with the group's one H instead: prod_S e(r_i pk_i, H) =
-  // e(sum_S r_i pk_i, H), the same pairing value, so the complement verdicts hold too
-  auto uflag = [&](uint32_t g) { return uniform && call->L.group_uniform[g] ? BGV_GROUP_UNIFORM : 0u; };
-  call->parts.clear();
-  call->punits.clear();
-  for (size_t ui = 0; ui < call->units.size(); ++ui) {
-    const auto& u = call->units[ui];
-    const int ug = call->unit_group[ui], urounds = call->unit_rounds[ui];
-    const bool in_group = unit_in_group(call, u, ug);
-    const bool eligible = gb >= 0 && in_group && urounds <= 0 && u.size() >= 2 && pattern_eligible(call, ui);
-    if (eligible && urounds == 0 && uflag((uint32_t)ug) && weighted_uniform_enabled()) {
-      // a failing uniform group almost always holds ONE invalid slot (a wrong key): one test with
-      // slot k weighted by k + 1 names it (BGV_GROUP_WEIGHTED; k_final12 finds w with V^w = W)
-      // instead of ~6 pattern tests of two Miller loops each; otherwise the pattern tests follow
-      // (unit_rounds -1).  Soundness with two or more invalid slots: write slot k's pairing
-      // defect as g^(e_k) in the prime-order group GT (e_k != 0 for an invalid slot; the
-      // signatures, hence the e_k, are the attacker's, fixed before the secret randomizers are
-      // drawn).  V^w = W means sum_k (k + 1 - w) r_k e_k = 0 (mod r), a linear equation in the
-      // secret r_k with a nonzero coefficient on at least one of them; r_k takes 2^64 distinct
-      // values mod r, so for one w it holds with probability <= 2^-64, and over the 64 candidate
-      // w with <= 64 * 2^-64 per failing group (a match would accept the other invalid jobs).
-      PatternUnit pu;
-      pu.group = (uint32_t)ug;
-      pu.kind = 2;
-      const bgv_dgroup& g = call->L.groups[pu.group];
-      std::vector<std::pair<uint32_t, size_t>> order;
-      for (size_t j : u) order.emplace_back(call->L.job_first_slot[j], j);
-      std::sort(order.begin(), order.end());
-      uint64_t m = 0;
-      for (const auto& o : order) {
-        pu.jobs.push_back(o.second);
-        m |= job_mask(call, o.second, g);
-      }
-      Part part;
-      part.jobs = pu.jobs;
-      part.groups.push_back((uint32_t)rg.size());
-      part.pattern = (int)call->punits.size();
-      pu.tests.push_back((uint32_t)rg.size());
-      rg.push_back(bgv_dgroup{call->slot_base + g.first_slot, g.n_slots, m, (uint32_t)(gb + ug + 1),
-                              BGV_GROUP_UNIFORM | BGV_GROUP_WEIGHTED});
-      call->parts.push_back(std::move(part));
-      call->punits.push_back(std::move(pu));
-      continue;
-    }
-    if (eligible) {
-      PatternUnit pu;
-      pu.group = (uint32_t)ug;
-      const bgv_dgroup& g = call->L.groups[pu.group];
-      std::vector<std::pair<uint32_t, size_t>> order;  // jobs in slot order
-      for (size_t j : u) order.emplace_back(call->L.job_first_slot[j], j);
-      std::sort(order.begin(), order.end());
-      std::vector<uint64_t> jmask;
-      for (const auto& o : order) {
-        pu.jobs.push_back(o.second);
-        jmask.push_back(job_mask(call, o.second, g));
-      }
-      const size_t n = pu.jobs.size();
-      int k = 0;
-      while ((1ull << k) < n) ++k;
-      for (int b = 0; b < k; ++b) {
-        uint64_t m = 0;
-        Part part;
-        for (size_t i = 0; i < n; ++i)
-          if ((i >> b) & 1) {
-            m |= jmask[i];
-            part.jobs.push_back(pu.jobs[i]);
-          }
-        pu.tests.push_back((uint32_t)rg.size());
-        part.groups.push_back((uint32_t)rg.size());
-        part.pattern = (int)call->punits.size();
-        rg.push_back(bgv_dgroup{call->slot_base + g.first_slot, g.n_slots, m, (uint32_t)(gb + ug + 1), uflag(ug)});
-        call->parts.push_back(std::move(part));
-      }
-      call->punits.push_back(std::move(pu));
-      continue;
-    }
-    if (in_group && urounds > 0 && call->unit_dmask[ui] && call->unit_idx[ui].size() == u.size()) {
-      // pairs x, x ^ D of a pattern round's candidates (see PatternUnit), single jobs otherwise
-      const bgv_dgroup& g = call->L.groups[ug];
-      const uint32_t D = call->unit_dmask[ui];
-      const uint32_t b0 = D & (~D + 1);  // lowest bit of D
-      std::unordered_map<uint32_t, size_t> at;
-      for (size_t k = 0; k < u.size(); ++k) at[call->unit_idx[ui][k]] = u[k];
-      PatternUnit pu;
-      pu.group = (uint32_t)ug;
-      pu.kind = 1;
-      for (size_t k = 0; k < u.size(); ++k) {
-        const uint32_t x = call->unit_idx[ui][k];
-        const auto partner = at.find(x ^ D);
-        if (partner != at.end() && (x & b0)) continue;  // tested with its partner
-        std::vector<size_t> tj{u[k]};
-        uint64_t m = job_mask(call, u[k], g);
-        if (partner != at.end()) {
-          tj.push_back(partner->second);
-          m |= job_mask(call, partner->second, g);
-        }
-        Part part;
-        part.jobs = tj;
-        part.groups.push_back((uint32_t)rg.size());
-        part.pattern = (int)call->punits.size();
-        pu.tests.push_back((uint32_t)rg.size());
-        pu.test_jobs.push_back(std::move(tj));
-        rg.push_back(bgv_dgroup{call->slot_base + g.first_slot, g.n_slots, m, 0, uflag(ug)});
-        call->parts.push_back(std::move(part));
-      }
-      call->punits.push_back(std::move(pu));
-      continue;
-    }
-    if (in_group && (urounds > 0 || u.size() <= kSingletonMax)) {
-      // one device group per job, each masked to the job's slots: every verdict in this round
-      const bgv_dgroup& g = call->L.groups[ug];
-      for (size_t j : u) {
-        Part part;
-        part.jobs.push_back(j);
-        part.groups.push_back((uint32_t)rg.size());
-        rg.push_back(bgv_dgroup{call->slot_base + g.first_slot, g.n_slots, job_mask(call, j, g), 0, uflag(ug)});
-        call->parts.push_back(std::move(part));
-      }
-      continue;
-    }
-    const size_t k = std::min<size_t>(retry_fanout(), u.size());
-    for (size_t p = 0; p < k; ++p) {
-      Part part;
-      const size_t lo = u.size() * p / k, hi = u.size() * (p + 1) / k;
-      part.jobs.assign(u.begin() + lo, u.begin() + hi);
-      for (size_t q = 0; q < part.jobs.size();) {  // maximal runs of consecutive slots
-        const uint32_t first = call->L.job_first_slot[part.jobs[q]];
-        uint32_t n = 0;
-        size_t q2 = q;
-        while (q2 < part.jobs.size() && call->L.job_first_slot[part.jobs[q2]] == first + n) {
-          n += call->jobs[part.jobs[q2]].n_sets;
-          ++q2;
-        }
-        // chunks within one first-pass group each, so a chunk of a uniform group takes its flag
-        // and its root: bounded by the end of slot s0's own group (with BGV_GROUP_SLOTS < 64 a
-        // wave holds several groups) and by the wave
-        for (uint32_t off = 0; off < n;) {
-          const uint32_t s0 = first + off;
-          const bgv_dgroup& g0 = call->L.groups[call->L.slots[s0].group];
-          const uint32_t len = std::min<uint32_t>(std::min<uint32_t>(n - off, BGV_WAVE - s0 % BGV_WAVE),
-                                                  g0.first_slot + g0.n_slots - s0);
-          part.groups.push_back((uint32_t)rg.size());
-          rg.push_back(bgv_dgroup{call->slot_base + s0, len, BGV_ALL_SLOTS, 0, uflag(call->L.slots[s0].group)});
-          off += len;
-        }
-        q = q2;
-      }
-      call->parts.push_back(std::move(part));
-    }
-  }
-  call->units.clear();
-  call->unit_group.clear();
-  call->unit_rounds.clear();
-  call->unit_idx.clear();
-  call->unit_dmask.clear();
-}
-
-static bool trace_on() {
-  static const bool v = getenv("BGV_TRACE") != nullptr;
-  return v;
-}
-
-// rv: the round's verdict bits (bgv_layout.h: bit 0 the group passes, bit 1 its pairing value
-// equals its reference's, i.e. the complement passes)
-static void call_after_round(Call* call, const int32_t* rv) {
-  for (const Part& part : call->parts) {
-    if (part.pattern >= 0) continue;
-    bool ok = true;
-    for (uint32_t g : part.groups) ok = ok && (rv[g] & 1);
-    if (ok || part.jobs.size() == 1) {
-      for (size_t j : part.jobs) call->code[j] = ok ? 1 : 0;
-    } else {
-      call->units.push_back(part.jobs);
-      call->unit_group.push_back(-1);
-      call->unit_rounds.push_back(0);
-      call->unit_idx.emplace_back();
-      call->unit_dmask.push_back(0);
-    }
-  }
-  for (const PatternUnit& pu : call->punits) {
-    if (pu.kind == 2) {  // one weighted test: bits 8..15 = w, slot w - 1 the lone invalid one
-      const int32_t v = rv[pu.tests[0]];
-      const uint32_t w = ((uint32_t)v >> 8) & 0xffu;
-      const bgv_dgroup& g = call->L.groups[pu.group];
-      size_t bad = SIZE_MAX;
-      if (w >= 1 && w <= g.n_slots)
-        for (size_t j : pu.jobs)
-          if ((job_mask(call, j, g) >> (w - 1)) & 1) bad = j;
-      if (bad != SIZE_MAX) {
-        for (size_t j : pu.jobs) call->code[j] = j == bad ? 0 : 1;
-      } else {  // not a lone invalid slot: the pattern tests next round
-        call->units.push_back(pu.jobs);
-        call->unit_group.push_back((int)pu.group);
-        call->unit_rounds.push_back(-1);
-        call->unit_idx.emplace_back();
-        call->unit_dmask.push_back(0);
-      }
-      continue;
-    }
-    if (pu.kind == 1) {  // pairs and single jobs (see PatternUnit)
-      std::vector<size_t> failing;
-      for (size_t t = 0; t < pu.tests.size(); ++t)
-        if (!(rv[pu.tests[t]] & 1)) failing.push_back(t);
-      std::vector<size_t> again;
-      for (size_t t = 0; t < pu.tests.size(); ++t) {
-        const auto& tj = pu.test_jobs[t];
-        const bool pass = rv[pu.tests[t]] & 1;
-        if (pass || tj.size() == 1 || failing.size() == 1) {
-          for (size_t j : tj) call->code[j] = pass ? 1 : 0;
-        } else {
-          again.insert(again.end(), tj.begin(), tj.end());
-        }
-      }
-      if (failing.empty()) again = [&] {  // never expected: every job alone
-        std::vector<size_t> all;
-        for (const auto& tj : pu.test_jobs) all.insert(all.end(), tj.begin(), tj.end());
-        return all;
-      }();
-      if (!again.empty()) {
-        call->units.push_back(again);
-        call->unit_group.push_back((int)pu.group);
-        call->unit_rounds.push_back(2);
-        call->unit_idx.emplace_back();
-        call->unit_dmask.push_back(0);
-      }
-      continue;
-    }
-    const size_t n = pu.jobs.size(), k = pu.tests.size();
-    std::vector<size_t> cand;
-    for (size_t i = 0; i < n; ++i) {
-      bool in_passing = false;  // in S_b (bit b of i set) or its complement, and that set passed
-      for (size_t b = 0; b < k && !in_passing; ++b) in_passing = (rv[pu.tests[b]] >> (((i >> b) & 1) ? 0 : 1)) & 1;
-      if (in_passing)
-        call->code[pu.jobs[i]] = 1;
-      else
-        cand.push_back(pu.jobs[i]);
-    }
-    if (trace_on()) fprintf(stderr, "[bgv]   pattern unit: %zu jobs, %zu tests, %zu candidates\n", n, k, cand.size());
-    if (cand.size() == 1) {
-      call->code[cand[0]] = 0;  // the group failed and every invalid job is a candidate
-    } else {
-      // two or more invalid jobs (or, never expected, none left: test every job alone); D =
-      // the bits where S_b and its complement both failed
-      uint32_t D = 0;
-      for (size_t b = 0; b < k; ++b)
-        if (!(rv[pu.tests[b]] & 1) && !((rv[pu.tests[b]] >> 1) & 1)) D |= 1u << b;
-      std::vector<uint32_t> idx;
-      if (!cand.empty())
-        for (size_t i = 0; i < n; ++i)
-          if (std::find(cand.begin(), cand.end(), pu.jobs[i]) != cand.end()) idx.push_back((uint32_t)i);
-      // every index bit with both S_b and its complement failing (D covers all k bits: every
-      // job a candidate) means many invalid jobs (two have all their index bits apart with
-      // probability 1/(n-1)): the next round tests them one by one (no D: singles) instead of
-      // pairs whose failures would need a third round
-#ifndef BGV_RETRY_ALLBITS_SINGLES
-#define BGV_RETRY_ALLBITS_SINGLES 1  // A/B: 0 keeps the pairs round for every unit with a D
-#endif
-      const bool all_bits = BGV_RETRY_ALLBITS_SINGLES && k > 0 && D == (k >= 32 ? 0xffffffffu : ((1u << k) - 1u));
-      call->units.push_back(cand.empty() ? pu.jobs : cand);
-      call->unit_group.push_back((int)pu.group);
-      call->unit_rounds.push_back(1);
-      call->unit_dmask.push_back(cand.empty() || all_bits ? 0 : D);
-      call->unit_idx.push_back(std::move(idx));
-    }
-  }
-  call->parts.clear();
-  call->punits.clear();
-}
-
 // Run one merged super-batch of calls on one dispatcher's stream.
 static double ms_since(std::chrono::steady_clock::time_point t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
-
 
 static bool needs_retry(const std::vector<Call*>& calls) {
   for (const Call* call : calls)
@@ -1541,10 +729,10 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
     uint32_t gb = 0;
     for (Call* call : calls) {
       call->st.device_ms += ms;
-      call_after_pass1(call, ss + call->slot_base, ps + call->slot_base, verdict + gb);
+      call->after_pass1(ss + call->slot_base, ps + call->slot_base, verdict + gb);
       call_gb.push_back(gb);
       gb += (uint32_t)call->L.groups.size();
-      for (size_t u = 0; u < call->units.size() && !want_gu; ++u) want_gu = pattern_eligible(call, u);
+      want_gu = want_gu || call->any_pattern_eligible();
     }
   }
   if (want_gu) {  // the first pass's u values of the groups, before a retry round reuses the array
@@ -1619,7 +807,7 @@ static int retry_launch(Device& d, RetryRun& r, bool* more) {
   const auto th = std::chrono::steady_clock::now();
   std::vector<bgv_dgroup> rg;
   for (size_t k = 0; k < calls.size(); ++k)
-    call_build_parts(calls[k], rg, bs.want_gu ? (int64_t)bs.call_gb[k] : -1, bs.uniform);
+    calls[k]->build_parts(rg, bs.want_gu ? (int64_t)bs.call_gb[k] : -1, bs.uniform);
   *more = !rg.empty();
   r.nrg = 0;
   if (rg.empty()) return BGV_OK;
@@ -1676,10 +864,7 @@ static int retry_complete(bgv_ctx* c, RetryRun& r, double t_wait) {
   }
   for (Call* call : r.job.calls) {
     call->st.device_ms += ms;
-    uint32_t mine = 0;
-    for (const Part& p : call->parts) mine += (uint32_t)p.groups.size();
-    call->st.device_groups += mine;
-    call_after_round(call, x.h_verdict.p);  // part group indices are global to this round
+    call->after_round(x.h_verdict.p);  // part group indices are global to this round
   }
   r.nrg = 0;
   return BGV_OK;
@@ -2175,10 +1360,34 @@ int bgv_pubkeys_put(bgv_ctx* c, uint32_t first, const uint8_t* keys, size_t n, i
 //     call pinned to its device (retry rounds stay on the device that ran the first pass).
 // Codes are those of the same call on one device (tests/test_gpu_r04.py).
 // ---------------------------------------------------------------------------
+static void fp12_one_bytes(uint8_t out[576]) {
+  memset(out, 0, 576);
+  out[47] = 1;  // c0.c0.c0 = 1, big-endian
+}
+
+// One job's sets -> its Fp12 Miller-loop product and status codes on device dev (-1: any).
 static int partial_submit(bgv_ctx* c, Call* call, const bgv_set* sets, size_t nsets, uint8_t* out576,
-                          int32_t* out_codes, int dev);
-static int call_wait(Call* call);
-static int partial_finish(Call* call, int rc, int32_t* out_codes);
+                          int32_t* out_codes, int dev) {
+  out_codes[0] = out_codes[1] = 0;
+  fp12_one_bytes(out576);
+  call->partial_out = out576;
+  call->partial_codes = out_codes;
+  call->pjob = bgv_job{0, (uint32_t)nsets, 0};
+  return call_submit(c, call, &call->pjob, 1, sets, nsets, BGV_MODE_PER_JOB, &call->pcode, nullptr, nullptr, nullptr,
+                     dev);
+}
+
+static int call_wait(Call* call) {
+  std::unique_lock<std::mutex> lk(call->mu);
+  call->cv.wait(lk, [call] { return call->finished; });
+  return call->rc;
+}
+
+static int partial_finish(Call* call, int rc, int32_t* out_codes) {
+  if (rc == BGV_OK) rc = call_wait(call);
+  if (rc == BGV_OK && call->pcode < 0 && call->pcode != -BGV_E_DEVICE) out_codes[0] = call->pcode;  // host-side
+  return rc;
+}
 
 static size_t split_min_sets(const bgv_ctx* c) {
   return c->split_min.load();
@@ -2395,35 +1604,6 @@ int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_se
   call->owned = true;  // deleted by the dispatcher after done()
   int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, done, user);
   if (rc != BGV_OK) delete call;
-  return rc;
-}
-
-static void fp12_one_bytes(uint8_t out[576]) {
-  memset(out, 0, 576);
-  out[47] = 1;  // c0.c0.c0 = 1, big-endian
-}
-
-// One job's sets -> its Fp12 Miller-loop product and status codes on device dev (-1: any).
-static int partial_submit(bgv_ctx* c, Call* call, const bgv_set* sets, size_t nsets, uint8_t* out576,
-                          int32_t* out_codes, int dev) {
-  out_codes[0] = out_codes[1] = 0;
-  fp12_one_bytes(out576);
-  call->partial_out = out576;
-  call->partial_codes = out_codes;
-  call->pjob = bgv_job{0, (uint32_t)nsets, 0};
-  return call_submit(c, call, &call->pjob, 1, sets, nsets, BGV_MODE_PER_JOB, &call->pcode, nullptr, nullptr, nullptr,
-                     dev);
-}
-
-static int call_wait(Call* call) {
-  std::unique_lock<std::mutex> lk(call->mu);
-  call->cv.wait(lk, [call] { return call->finished; });
-  return call->rc;
-}
-
-static int partial_finish(Call* call, int rc, int32_t* out_codes) {
-  if (rc == BGV_OK) rc = call_wait(call);
-  if (rc == BGV_OK && call->pcode < 0 && call->pcode != -BGV_E_DEVICE) out_codes[0] = call->pcode;  // host-side
   return rc;
 }
 

@@ -37,7 +37,7 @@ enum {
 };
 
 // A device group: the slots first_slot + k, k < n_slots, whose bit k of mask is set (retry
-// rounds test job subsets that are not contiguous: bgv_api.cpp pattern tests).  ref1 != 0
+// rounds test job subsets that are not contiguous: bgv_retry_plan.h pattern tests).  ref1 != 0
 // names the first-pass group (index ref1 - 1 of the batch) whose pairing value this group's
 // is compared with: the closing then also reports whether the two values agree, i.e. whether
 // the rest of that group (its complement) passes (verdict bit 1).
@@ -54,10 +54,10 @@ struct bgv_dgroup {
 // never retried).  prod_i e(r_i pk_i, H) = e(sum_i r_i pk_i, H),
 // so the group's set pairs are ONE Miller loop over its pubkey sum (k_gsum -> gpk, k_facc ->
 // gpkp) and its slots take none; a retry test inside such a group (flagged the same,
-// bgv_api.cpp call_build_parts) pairs the sum of its own slots' r_i pk_i the same way
+// bgv_retry_plan.h build_parts) pairs the sum of its own slots' r_i pk_i the same way
 #define BGV_GROUP_UNIFORM 4u
 // flags: a retry test over a whole failing uniform group with slot k weighted by k + 1
-// (bgv_api.cpp PatternUnit kind 2): k_gsum forms sum (k+1) r_k sig_k and sum (k+1) r_k pk_k,
+// (bgv_retry_plan.h PatternUnit Weighted): k_gsum forms sum (k+1) r_k sig_k and sum (k+1) r_k pk_k,
 // and k_final12 reports in verdict bits 8..15 the w <= n_slots with V^w = W against the
 // first-pass value V of group ref1 - 1 (0: none) -- the slot w - 1 when exactly one is invalid
 #define BGV_GROUP_WEIGHTED 8u
