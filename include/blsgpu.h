@@ -138,6 +138,57 @@ typedef void (*bgv_done_fn)(void* user, int rc);
 int bgv_verify_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
                      int32_t* out_job_codes, bgv_stats* stats, bgv_done_fn done, void* user);
 
+/* Committee-bitfield signature sets ------------------------------------------
+ * The beacon node never starts from a list of attesting validators: it holds a committee
+ * (an epoch shuffling's, or the 512-member sync committee) and a participation bitfield and
+ * expands them with bits.intersectValues(committeeIndices)
+ * (state-transition/src/cache/epochContext.ts:620-622, block/processSyncCommittee.ts:16,77,
+ * block/processAttestationsAltair.ts:50).  Here a committee is uploaded once and a set names
+ * (committee, bitfield): the device keeps the committee's index table and its full pubkey sum
+ * and adds whichever side is shorter -- the participants, or the absentees subtracted from the
+ * total.  The aggregate is the same group element, so verdicts are those of the expanded list.
+ *
+ * bgv_committee_put stores indices[0, n) (1 <= n <= 65536) under id < BGV_MAX_COMMITTEES on every
+ * device of the context and computes their pubkey sum there.  Every index must be below
+ * bgv_pubkeys_count and not marked undecodable (-BGV_E_BAD_INDEX, nothing stored); a put on an id
+ * that is still live returns -BGV_E_ARG.  A put never waits for running verifies unless the
+ * device's index pool has to grow.  A bgv_pubkeys_put (or bgv_keygen) over existing indices
+ * recomputes the sums of the live committees that hold one of them before it returns; a committee
+ * that then holds a marked key makes every set naming it reject with BGV_E_BAD_INDEX.  A dropped
+ * committee that a queued call still names is recomputed the same way.
+ * bgv_committee_drop frees the id for reuse at once (-BGV_E_BAD_INDEX: no such committee); the
+ * device storage is reused only after the calls laid out before the drop have finished. */
+#define BGV_MAX_COMMITTEES 16384 /* ids 0..16383: 3 epochs x 2048 committees + sync committees */
+#define BGV_NO_COMMITTEE 0xFFFFFFFFu
+int bgv_committee_put(bgv_ctx* ctx, uint32_t id, const uint32_t* indices, size_t n);
+int bgv_committee_drop(bgv_ctx* ctx, uint32_t id);
+
+/* The pubkeys of one set as committee members: member k takes part iff
+ * (bits[k >> 3] >> (k & 7)) & 1 (SSZ bit order); bits holds ceil(n_bits / 8) bytes.
+ * committee == BGV_NO_COMMITTEE: the set's own pk_indices / pk_bytes count. */
+typedef struct {
+  uint32_t committee;
+  uint32_t n_bits;
+  const uint8_t* bits;
+} bgv_pkbits;
+
+/* bgv_verify / bgv_verify_async with pkbits[i] beside sets[i] (pkbits may be NULL: bgv_verify).
+ * Where pkbits[i].committee != BGV_NO_COMMITTEE, set i's n_pk, pk_indices and pk_bytes are
+ * ignored.  The host's argument checks give the job of a malformed set its code, as for index
+ * sets: an unknown or dropped id -BGV_E_BAD_INDEX, n_bits other than the committee's length
+ * -BGV_E_ARG, a set bit at or past n_bits in the last byte -BGV_E_ARG, no bit set
+ * -BGV_E_EMPTY_AGGREGATE.  Everything else is the call with the expanded index list. */
+int bgv_verify_bits(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                    const bgv_pkbits* pkbits, int mode, int32_t* out_job_codes, bgv_stats* stats);
+int bgv_verify_bits_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                          const bgv_pkbits* pkbits, int mode, int32_t* out_job_codes, bgv_stats* stats,
+                          bgv_done_fn done, void* user);
+
+/* Parity hook beside bgv_aggregate_pubkeys: the aggregate of a committee's selected members
+ * through the verify path's own kernel (k_pk_agg_bits, the side the layout would take),
+ * 96-byte uncompressed encoding (0x40 for infinity).  Codes as the set checks above. */
+int bgv_aggregate_committee_bits(bgv_ctx* ctx, uint32_t id, const uint8_t* bits, uint32_t n_bits, uint8_t out96[96]);
+
 /* Parity hook for bls.PublicKey.aggregate + toBytes(uncompressed)
  * (chain/bls/utils.ts:5-16, multithread/index.ts:160): sum of cached pubkeys,
  * 96-byte uncompressed ZCash encoding (0x40 flag for infinity). */

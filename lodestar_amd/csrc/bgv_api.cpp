@@ -31,6 +31,7 @@
 #include <condition_variable>
 #include <unordered_map>
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -178,6 +179,64 @@ struct FinalScratch {
   size_t cap = 0;
 };
 
+// Device-resident committees (bgv_committee_put).  Every device keeps a directory of
+// kComHandles entries (bgv_dcommittee: where the members are, how many, their pubkey sum) and one
+// pool of member indices; a committee has the same handle and pool range on every device.  The
+// host maps the caller's ids to handles: a set is laid out with the HANDLE, and every call holds
+// a reference to the committees it names, so a drop (and a put that reuses the id) never changes
+// what a call laid out before it reads -- the handle and the pool range return to the free lists
+// when the last reference goes, i.e. after those calls have finished.
+static const uint32_t kComHandles = 2 * BGV_MAX_COMMITTEES;  // live ones plus dropped ones still referenced
+static const size_t kComPoolInit = size_t(1) << 20;          // member indices (4 MB), doubled on demand
+struct ComPool {
+  std::mutex mu;
+  std::vector<uint32_t> free_handles;
+  std::map<uint32_t, uint32_t> free_ranges;  // offset -> length, coalesced
+  size_t cap = 0;
+  bool alloc(uint32_t n, uint32_t* handle, uint32_t* off) {  // under mu
+    if (free_handles.empty()) return false;
+    for (auto it = free_ranges.begin(); it != free_ranges.end(); ++it)
+      if (it->second >= n) {
+        *off = it->first;
+        const uint32_t rest = it->second - n;
+        free_ranges.erase(it);
+        if (rest) free_ranges.emplace(*off + n, rest);
+        *handle = free_handles.back();
+        free_handles.pop_back();
+        return true;
+      }
+    return false;
+  }
+  void add_range(uint32_t off, uint32_t n) {  // under mu
+    auto nx = free_ranges.lower_bound(off);
+    if (nx != free_ranges.begin()) {
+      auto pv = std::prev(nx);
+      if (pv->first + pv->second == off) {
+        off = pv->first;
+        n += pv->second;
+        free_ranges.erase(pv);
+      }
+    }
+    if (nx != free_ranges.end() && off + n == nx->first) {
+      n += nx->second;
+      free_ranges.erase(nx);
+    }
+    free_ranges.emplace(off, n);
+  }
+};
+struct CommitteeRec {
+  uint32_t handle = 0, off = 0;
+  std::vector<uint32_t> idx;  // the members (host mirror: set checks, recomputing after a pubkey overwrite)
+  bool bad = false;           // holds a marked key (written under the exclusive cache_mu)
+  std::shared_ptr<ComPool> pool;
+  ~CommitteeRec() {
+    if (!pool) return;
+    std::lock_guard<std::mutex> lk(pool->mu);
+    pool->free_handles.push_back(handle);
+    pool->add_range(off, (uint32_t)idx.size());
+  }
+};
+
 struct Call;
 // What a super-batch's retry rounds need from its first pass.
 struct BatchState {
@@ -220,6 +279,9 @@ struct Device {
   hipStream_t stream = nullptr;      // utility work (cache upload, hooks, keygen)
   bgv_cache_entry* cache = nullptr;  // pubkey cache (replicated on every device)
   size_t cache_cap = 0;
+  bgv_dcommittee* com_dir = nullptr;  // kComHandles entries
+  uint32_t* com_pool = nullptr;       // member indices of every committee (ComPool::cap words)
+  uint32_t* com_list = nullptr;       // kComHandles words: the handles of one k_committee_total launch
   std::vector<Exec*> execs;
   // held while one super-batch runs its per-set kernels (pointer: Device stays movable)
   std::unique_ptr<std::mutex> compute_mu = std::make_unique<std::mutex>();
@@ -229,6 +291,9 @@ struct Device {
 // units: CallPlan, bgv_retry_plan.h) and how its caller hears of the end.
 struct Call : CallPlan {
   const bgv_set* sets = nullptr;
+  const bgv_pkbits* pkbits = nullptr;                   // per set, or null (bgv_verify_bits)
+  std::vector<SetCommittee> setcom;                     // per set once checked (empty without pkbits)
+  std::vector<std::shared_ptr<CommitteeRec>> com_refs;  // the committees the layout names
   int32_t* out = nullptr;
   bgv_stats* stats_out = nullptr;
   bgv_done_fn done = nullptr;
@@ -263,6 +328,14 @@ struct bgv_ctx {
   uint64_t rng_seed = 0, rng_state = 0;
   std::shared_mutex cache_mu;  // verify: shared; cache writes: exclusive
   std::mutex util_mu;          // utility streams
+  // live committees by id (com_mu: a call's checks read it shared, once per call; puts and drops,
+  // serialised by put_mu, write it exclusively).  Lock order: cache_mu, then com_mu.
+  std::shared_mutex com_mu;
+  std::unordered_map<uint32_t, std::shared_ptr<CommitteeRec>> committees;
+  // dropped committees that queued calls may still name (expired entries are pruned at the next
+  // drop): a pubkey overwrite recomputes their sums too
+  std::vector<std::weak_ptr<CommitteeRec>> retired;
+  std::shared_ptr<ComPool> com_pool = std::make_shared<ComPool>();
   std::mutex prof_mu;
   bool profile = false;
   // BGV_FAULT_INJECT=1 at bgv_init: every super-batch fails as a HIP error would (tests of
@@ -452,6 +525,8 @@ static bgv_dev_batch make_batch(Device& d, Exec& x, uint32_t nslots, uint32_t ng
   b.pk_idx = x.d_idx;
   b.cache_opaque = d.cache;
   b.pk_bytes = x.d_pkb;
+  b.com_dir = d.com_dir;
+  b.com_pool = d.com_pool;
   bgv_carve(&b, x.slot_mem, x.slot_cap, x.group_mem, x.group_cap);
   return b;
 }
@@ -487,7 +562,12 @@ static void call_fail(Call* call, int rc) {
 // job goes to the device, else its verdict (empty job, empty aggregate, an index that is not
 // in the cache -- the first such set in set order).  -BGV_E_ARG for a malformed set record.
 // The caller holds cache_mu (shared).
-static int host_job_code(const bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code) {
+// A committee set (pkbits[i].committee != BGV_NO_COMMITTEE) is checked against the live
+// committee of its id (committee_set_check); with a call, what the layout needs of it goes to
+// call->setcom and the call takes a reference to the committee.  The caller holds com_mu (shared)
+// when pkbits is given.
+static int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code,
+                         const bgv_pkbits* pkbits = nullptr, Call* call = nullptr) {
   *code = 2;
   if (jb.n_sets == 0) {
     *code = -BGV_E_EMPTY_SET;
@@ -495,6 +575,21 @@ static int host_job_code(const bgv_ctx* c, const bgv_job& jb, const bgv_set* set
   }
   for (uint32_t k = 0; k < jb.n_sets && *code == 2; ++k) {
     const bgv_set& s = sets[jb.first_set + k];
+    if (pkbits && pkbits[jb.first_set + k].committee != BGV_NO_COMMITTEE) {
+      const bgv_pkbits& pb = pkbits[jb.first_set + k];
+      if (!s.msg || (!s.sig && s.sig_len) || (!pb.bits && pb.n_bits)) return -BGV_E_ARG;
+      const auto it = c->committees.find(pb.committee);
+      const CommitteeRec* rec = it != c->committees.end() ? it->second.get() : nullptr;
+      CommitteeInfo ci{};
+      if (rec) ci = CommitteeInfo{rec->handle, (uint32_t)rec->idx.size(), rec->bad};
+      SetCommittee sc;
+      *code = committee_set_check(rec ? &ci : nullptr, pb, &sc);
+      if (*code == 2 && call) {
+        call->setcom[jb.first_set + k] = sc;
+        if (call->com_refs.empty() || call->com_refs.back().get() != rec) call->com_refs.push_back(it->second);
+      }
+      continue;
+    }
     if (s.n_pk == 0)
       *code = -BGV_E_EMPTY_AGGREGATE;
     else if (!s.msg || (!s.sig && s.sig_len) || (!s.pk_indices && !s.pk_bytes))
@@ -520,7 +615,8 @@ static void advise_huge(void* p, size_t bytes) {
 
 // host-side checks and layout, on the caller's thread
 static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
-                       int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user, int dev = -1) {
+                       int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user, int dev = -1,
+                       const bgv_pkbits* pkbits = nullptr) {
   call->t0 = std::chrono::steady_clock::now();
   call->dev = dev;
   if (c->closed) return -BGV_E_CLOSED;
@@ -536,19 +632,27 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
   call->done = done;
   call->user = user;
   call->code.assign(njobs, 2);
+  call->pkbits = pkbits;
+  if (pkbits) call->setcom.assign(nsets, SetCommittee{});
   {
     std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+    std::shared_lock<std::shared_mutex> mlk(c->com_mu, std::defer_lock);
+    if (pkbits) mlk.lock();
     for (size_t j = 0; j < njobs; ++j) {
       if ((size_t)jobs[j].first_set + jobs[j].n_sets > nsets) return -BGV_E_ARG;
-      if (host_job_code(c, jobs[j], sets, &call->code[j]) != BGV_OK) return -BGV_E_ARG;
+      if (host_job_code(c, jobs[j], sets, &call->code[j], pkbits, call) != BGV_OK) return -BGV_E_ARG;
     }
   }
+  const auto is_com = [pkbits](size_t i) { return pkbits && pkbits[i].committee != BGV_NO_COMMITTEE; };
   // pass-1 layout (bgv_host_layout.h)
   Layout& L = call->L;
   {
     size_t npk = 0;
     for (size_t i = 0; i < nsets; ++i)
-      if (sets[i].pk_indices) npk += sets[i].n_pk;
+      if (is_com(i))
+        npk += 1 + pkb_nwords(call->setcom[i].n);  // the handle and the bit words (a refused set: n = 0)
+      else if (sets[i].pk_indices)
+        npk += sets[i].n_pk;
     const size_t cap = nsets + nsets / 8 + BGV_WAVE;  // with room for the groups' padding
     L.slots.reserve(cap);
     L.slot_set.reserve(cap);
@@ -559,7 +663,7 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
       advise_huge(L.idx.data(), 4 * npk);
     }
   }
-  layout_call(L, call->todo, jobs, njobs, sets, mode, call->code);
+  layout_call(L, call->todo, jobs, njobs, sets, mode, call->code, pkbits ? call->setcom.data() : nullptr);
   call->set_sig.assign(nsets, 0);
   call->set_pk.assign(nsets, 0);
   if (L.slots.empty()) {  // nothing for the device
@@ -597,7 +701,7 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   double t_merge = 0, t_tok = 0, t_sets = 0, t_pass1 = 0, t_post = 0;
   // merge the calls' layouts
   uint32_t nslots = 0, ngroups = 0;
-  size_t nidx = 0, npkb = 0, nuniq = 0;
+  size_t nidx = 0, npkb = 0, nuniq = 0, ncom_team = 0, ncom_wave = 0;
   bool any_uniform = false;
   for (Call* call : calls) {
     call->slot_base = nslots;
@@ -606,20 +710,23 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
     nidx += call->L.idx.size();
     npkb += call->L.pkb.size();
     nuniq += call->L.uniq.size();
+    ncom_team += call->L.com_team.size();
+    ncom_wave += call->L.com_wave.size();
     for (char u : call->L.group_uniform) any_uniform = any_uniform || u;
   }
+  const size_t ncom = ncom_team + ncom_wave, nlist = nuniq + ncom;  // the lists after the indices
   const bool bulk = nslots + ngroups > bgv_fold_pairs_max();
   // uniform groups (BGV_GROUP_UNIFORM): bulk batches on the two-phase Miller stage
   const bool uniform = uniform_enabled() && any_uniform && bulk && !bgv_single_pass_miller();
   HIPCHK(hipSetDevice(d.id));
   int rc;
   if ((rc = exec_reserve_slots(x, nslots)) || (rc = exec_reserve_groups(x, ngroups)) ||
-      (rc = grow(&x.d_idx, &x.idx_cap, std::max<size_t>(nidx + nuniq, 1))) ||
+      (rc = grow(&x.d_idx, &x.idx_cap, std::max<size_t>(nidx + nlist, 1))) ||
       (rc = grow(&x.d_pkb, &x.pkb_cap, std::max<size_t>(npkb, 1))))
     return rc;
   HIPCHK(x.h_slots.reserve(nslots));
   HIPCHK(x.h_groups.reserve(std::max<size_t>(ngroups, 1)));
-  HIPCHK(x.h_idx.reserve(nidx + nuniq));  // pubkey indices, then the hashed slots (b.uniq)
+  HIPCHK(x.h_idx.reserve(nidx + nlist));  // pubkey indices, the hashed slots (b.uniq), the committee slots (b.com)
   HIPCHK(x.h_pkb.reserve(npkb));
   HIPCHK(x.h_ss.reserve(nslots));
   HIPCHK(x.h_ps.reserve(nslots));
@@ -637,7 +744,8 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
         par_ranges(call->L.slots.size(), [&](size_t lo, size_t hi) {
           memcpy(slots + lo, src + lo, sizeof(bgv_dslot) * (hi - lo));
           uint32_t m = 0;
-          for (size_t i = lo; i < hi; ++i) m = std::max(m, src[i].n_pk);
+          for (size_t i = lo; i < hi; ++i)  // a committee slot's n_pk is no run of indices (k_pk_agg_bits sums it)
+            if (!(src[i].flags & BGV_SLOT_PK_COMMITTEE)) m = std::max(m, src[i].n_pk);
           uint32_t cur = mx.load();
           while (m > cur && !mx.compare_exchange_weak(cur, m)) {
           }
@@ -645,12 +753,9 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
         max_npk = std::max(max_npk, mx.load());
         ns = call->L.slots.size();
       } else {
-        for (bgv_dslot s : call->L.slots) {
-          s.hsrc += call->slot_base;
-          if (s.flags & BGV_SLOT_PK_CACHED) s.pk_off += ib;
-          if (s.flags & BGV_SLOT_PK_BYTES) s.pk_off += pb;
-          if (!(s.flags & BGV_SLOT_PAD)) s.group += gb;
-          max_npk = std::max(max_npk, s.n_pk);
+        for (const bgv_dslot& s0 : call->L.slots) {
+          const bgv_dslot s = rebase_slot(s0, call->slot_base, ib, pb, gb);
+          if (!(s.flags & BGV_SLOT_PK_COMMITTEE)) max_npk = std::max(max_npk, s.n_pk);
           slots[ns++] = s;
         }
       }
@@ -667,6 +772,10 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
     uint32_t* u = x.h_idx.p + nidx;
     for (Call* call : calls)
       for (uint32_t v : call->L.uniq) *u++ = v + call->slot_base;
+    for (Call* call : calls)
+      for (uint32_t v : call->L.com_team) *u++ = v + call->slot_base;
+    for (Call* call : calls)
+      for (uint32_t v : call->L.com_wave) *u++ = v + call->slot_base;
   }
   std::vector<uint64_t> sc(nslots);
   fill_scalars(c, sc.data(), nslots);
@@ -683,7 +792,7 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   if (c->fault_inject) HIPCHK(hipErrorLaunchFailure);
   HIPCHK(hipMemcpyAsync(x.d_slots, slots, sizeof(bgv_dslot) * nslots, hipMemcpyHostToDevice, x.main));
   HIPCHK(hipMemcpyAsync(x.d_groups, groups, sizeof(bgv_dgroup) * ngroups, hipMemcpyHostToDevice, x.main));
-  if (nidx + nuniq) HIPCHK(hipMemcpyAsync(x.d_idx, x.h_idx.p, 4 * (nidx + nuniq), hipMemcpyHostToDevice, x.main));
+  if (nidx + nlist) HIPCHK(hipMemcpyAsync(x.d_idx, x.h_idx.p, 4 * (nidx + nlist), hipMemcpyHostToDevice, x.main));
   if (npkb) HIPCHK(hipMemcpyAsync(x.d_pkb, x.h_pkb.p, npkb, hipMemcpyHostToDevice, x.main));
   bgv_dev_batch b = make_batch(d, x, nslots, ngroups);
   b.max_npk = max_npk;
@@ -691,6 +800,9 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   bs.uniform = uniform;
   b.uniq = x.d_idx + nidx;
   b.nuniq = (uint32_t)nuniq;
+  b.com = x.d_idx + nidx + nuniq;
+  b.ncom_team = (uint32_t)ncom_team;
+  b.ncom_wave = (uint32_t)ncom_wave;
   if (int lrc = exec_reserve_lines(x, b)) return lrc;
   bgv_streams S{x.main, prof ? x.kev : nullptr};
   int32_t *ss = x.h_ss.p, *ps = x.h_ps.p, *verdict = x.h_verdict.p;
@@ -1068,6 +1180,14 @@ static void ctx_free_devices(bgv_ctx* c) {
     if (d.cache) (void)hipFree(d.cache);
     d.cache = nullptr;
     {
+      void* cbufs[] = {d.com_dir, d.com_pool, d.com_list};
+      for (void* q : cbufs)
+        if (q) (void)hipFree(q);
+      d.com_dir = nullptr;
+      d.com_pool = nullptr;
+      d.com_list = nullptr;
+    }
+    {
       FinalScratch& fs = d.final_scratch;
       void* bufs[] = {fs.din, fs.vals, fs.one, fs.dg, fs.dst, fs.dv};
       for (void* q : bufs)
@@ -1114,6 +1234,10 @@ int bgv_init(const int* devices, int ndev, bgv_ctx** out) {
       ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
       if (ok) d.sched->dstreams.push_back(st);
     }
+    // the committee directory and index pool (bgv_committee_put)
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&d.com_dir), sizeof(bgv_dcommittee) * kComHandles) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&d.com_pool), 4 * kComPoolInit) == hipSuccess &&
+         hipMalloc(reinterpret_cast<void**>(&d.com_list), 4 * (size_t)kComHandles) == hipSuccess;
     for (int k = 0; ok && k < execs_per_device(); ++k) {
       Exec* x = new Exec();
       d.execs.push_back(x);
@@ -1127,6 +1251,9 @@ int bgv_init(const int* devices, int ndev, bgv_ctx** out) {
       return d.id < 0 || d.id >= avail ? -BGV_E_ARG : -BGV_E_DEVICE;
     }
   }
+  c->com_pool->cap = kComPoolInit;
+  c->com_pool->free_ranges.emplace(0u, (uint32_t)kComPoolInit);
+  for (uint32_t h = kComHandles; h-- > 0;) c->com_pool->free_handles.push_back(h);
   for (Device& d : c->devs) {
     for (hipStream_t st : d.sched->dstreams) c->dispatchers.emplace_back(dispatcher_loop, c, &d, st);
     for (int k = 0; k < (int)d.sched->retries.size(); ++k) d.sched->retry_threads.emplace_back(retry_loop, c, &d, k);
@@ -1210,6 +1337,139 @@ static int cache_reserve(bgv_ctx* c, size_t need) {
     d.cache = static_cast<bgv_cache_entry*>(p);
     d.cache_cap = cap;
   }
+  return BGV_OK;
+}
+
+// The pubkey sums of the committees in handles, on every device (k_committee_total on the
+// utility streams).  The caller holds what keeps the utility streams its own (util_mu, or the
+// exclusive cache_mu) and, for committees that are live, the exclusive cache_mu.
+static int committee_totals(bgv_ctx* c, const std::vector<uint32_t>& handles) {
+  if (handles.empty()) return BGV_OK;
+  for (Device& d : c->devs) {
+    HIPCHK(hipSetDevice(d.id));
+    HIPCHK(hipMemcpyAsync(d.com_list, handles.data(), 4 * handles.size(), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(bgv_launch_committee_totals(d.com_dir, d.com_list, (uint32_t)handles.size(), d.com_pool, d.cache, d.stream));
+    HIPCHK(hipStreamSynchronize(d.stream));
+  }
+  return BGV_OK;
+}
+
+// After cache entries [first, first + n) were overwritten: the committees that hold one of them
+// -- the live ones, and the dropped ones a queued call still names -- get their sums recomputed
+// and their marked-key flag refreshed.  Under the exclusive
+// cache_mu (no verify reads a directory entry meanwhile).
+static int committees_refresh(bgv_ctx* c, uint32_t first, size_t n) {
+  std::vector<uint32_t> handles;
+  {
+    std::unique_lock<std::shared_mutex> lk(c->com_mu);
+    std::vector<std::shared_ptr<CommitteeRec>> recs;
+    for (auto& kv : c->committees) recs.push_back(kv.second);
+    for (auto& w : c->retired)
+      if (auto sp = w.lock()) recs.push_back(std::move(sp));
+    for (auto& sp : recs) {
+      CommitteeRec& r = *sp;
+      bool touched = false, bad = false;
+      for (uint32_t i : r.idx) {
+        touched = touched || (i >= first && (size_t)i < (size_t)first + n);
+        bad = bad || (!c->bad_pk.empty() && c->bad_pk.count(i));
+      }
+      if (!touched) continue;
+      r.bad = bad;
+      handles.push_back(r.handle);
+    }
+  }
+  return committee_totals(c, handles);
+}
+
+// the devices' index pools grown to hold `need` more words; under the exclusive cache_mu
+static int com_pool_grow(bgv_ctx* c, size_t need) {
+  ComPool& P = *c->com_pool;
+  const size_t old = P.cap, cap = std::max(2 * old, old + need);
+  if (cap > (size_t)UINT32_MAX) return -BGV_E_NOMEM;
+  for (Device& d : c->devs) {
+    HIPCHK(hipSetDevice(d.id));
+    uint32_t* p = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), 4 * cap));
+    HIPCHK(hipMemcpyAsync(p, d.com_pool, 4 * old, hipMemcpyDeviceToDevice, d.stream));
+    HIPCHK(hipStreamSynchronize(d.stream));
+    HIPCHK(hipFree(d.com_pool));
+    d.com_pool = p;
+  }
+  std::lock_guard<std::mutex> lk(P.mu);
+  P.add_range((uint32_t)old, (uint32_t)(cap - old));
+  P.cap = cap;
+  return BGV_OK;
+}
+
+int bgv_committee_put(bgv_ctx* c, uint32_t id, const uint32_t* indices, size_t n) {
+  if (!c || id >= BGV_MAX_COMMITTEES || !indices || n < 1 || n > 65536) return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  auto rec = std::make_shared<CommitteeRec>();
+  // the checks, then the upload into a handle and a pool range no laid-out call names, and the
+  // sum; under the shared cache lock (verifies go on) unless the pool has to grow
+  auto checks = [&]() -> int {
+    if (c->closed) return -BGV_E_CLOSED;
+    {
+      std::shared_lock<std::shared_mutex> lk(c->com_mu);
+      if (c->committees.count(id)) return -BGV_E_ARG;
+    }
+    for (size_t i = 0; i < n; ++i)
+      if (indices[i] >= c->n_pubkeys || (!c->bad_pk.empty() && c->bad_pk.count(indices[i]))) return -BGV_E_BAD_INDEX;
+    return BGV_OK;
+  };
+  auto take = [&]() -> bool {
+    std::lock_guard<std::mutex> lk(c->com_pool->mu);
+    if (!c->com_pool->alloc((uint32_t)n, &rec->handle, &rec->off)) return false;
+    rec->pool = c->com_pool;  // from here on the record gives both back
+    return true;
+  };
+  auto upload = [&]() -> int {
+    rec->idx.assign(indices, indices + n);
+    const bgv_dcommittee head{rec->off, (uint32_t)n, {}};
+    std::lock_guard<std::mutex> ulk(c->util_mu);
+    for (Device& d : c->devs) {
+      HIPCHK(hipSetDevice(d.id));
+      HIPCHK(hipMemcpyAsync(d.com_pool + rec->off, indices, 4 * n, hipMemcpyHostToDevice, d.stream));
+      HIPCHK(hipMemcpyAsync(d.com_dir + rec->handle, &head, sizeof(head), hipMemcpyHostToDevice, d.stream));
+      HIPCHK(hipStreamSynchronize(d.stream));  // head is on this stack
+    }
+    const int rc = committee_totals(c, {rec->handle});
+    if (rc) return rc;
+    std::unique_lock<std::shared_mutex> lk(c->com_mu);
+    c->committees.emplace(id, rec);
+    return BGV_OK;
+  };
+  {
+    std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+    if (int rc = checks()) return rc;
+    if (take()) return upload();
+    std::lock_guard<std::mutex> lk(c->com_pool->mu);
+    if (c->com_pool->free_handles.empty()) return -BGV_E_NOMEM;  // every handle is live or still referenced
+  }
+  std::unique_lock<std::shared_mutex> clk(c->cache_mu);
+  if (int rc = checks()) return rc;
+  {
+    std::lock_guard<std::mutex> ulk(c->util_mu);
+    if (int rc = com_pool_grow(c, n)) return rc;
+  }
+  if (!take()) return -BGV_E_NOMEM;
+  return upload();
+}
+
+int bgv_committee_drop(bgv_ctx* c, uint32_t id) {
+  if (!c) return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  if (c->closed) return -BGV_E_CLOSED;
+  std::shared_ptr<CommitteeRec> rec;  // released after com_mu: the last reference frees the handle
+  std::unique_lock<std::shared_mutex> lk(c->com_mu);
+  auto it = c->committees.find(id);
+  if (it == c->committees.end()) return -BGV_E_BAD_INDEX;
+  rec = std::move(it->second);
+  c->committees.erase(it);
+  c->retired.erase(std::remove_if(c->retired.begin(), c->retired.end(),
+                                  [](const std::weak_ptr<CommitteeRec>& w) { return w.expired(); }),
+                   c->retired.end());
+  c->retired.push_back(rec);
   return BGV_OK;
 }
 
@@ -1338,6 +1598,7 @@ int bgv_pubkeys_put(bgv_ctx* c, uint32_t first, const uint8_t* keys, size_t n, i
         for (uint32_t i = first; i < need; ++i) c->bad_pk.erase(i);  // overwritten entries
         for (uint32_t i : bad) c->bad_pk.insert(i);
         c->n_pubkeys.store(std::max(c->n_pubkeys.load(), need));
+        if (first < old_n) rc = committees_refresh(c, first, n);  // live committees over these keys
       }
     }
   }
@@ -1367,14 +1628,14 @@ static void fp12_one_bytes(uint8_t out[576]) {
 
 // One job's sets -> its Fp12 Miller-loop product and status codes on device dev (-1: any).
 static int partial_submit(bgv_ctx* c, Call* call, const bgv_set* sets, size_t nsets, uint8_t* out576,
-                          int32_t* out_codes, int dev) {
+                          int32_t* out_codes, int dev, const bgv_pkbits* pkbits = nullptr) {
   out_codes[0] = out_codes[1] = 0;
   fp12_one_bytes(out576);
   call->partial_out = out576;
   call->partial_codes = out_codes;
   call->pjob = bgv_job{0, (uint32_t)nsets, 0};
   return call_submit(c, call, &call->pjob, 1, sets, nsets, BGV_MODE_PER_JOB, &call->pcode, nullptr, nullptr, nullptr,
-                     dev);
+                     dev, pkbits);
 }
 
 static int call_wait(Call* call) {
@@ -1422,8 +1683,8 @@ static void split_leave(bgv_ctx* c) {
   c->split_cv.notify_all();
 }
 
-static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
-                        int32_t* out, bgv_stats* stats) {
+static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                        const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   const size_t K = c->devs.size(), big = split_min_sets(c);
   struct Shard {  // one run of a big job on one device
@@ -1450,9 +1711,11 @@ static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv
   std::vector<int32_t> pre(njobs, 2);
   {
     std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+    std::shared_lock<std::shared_mutex> mlk(c->com_mu, std::defer_lock);
+    if (pkbits) mlk.lock();
     for (size_t j = 0; j < njobs; ++j) {
       if ((size_t)jobs[j].first_set + jobs[j].n_sets > nsets) return -BGV_E_ARG;
-      if (jobs[j].n_sets >= big && host_job_code(c, jobs[j], sets, &pre[j]) != BGV_OK) return -BGV_E_ARG;
+      if (jobs[j].n_sets >= big && host_job_code(c, jobs[j], sets, &pre[j], pkbits) != BGV_OK) return -BGV_E_ARG;
     }
   }
   for (size_t j = 0; j < njobs; ++j) {
@@ -1480,7 +1743,7 @@ static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv
         }
       kid->out.assign(kid->jobs.size(), 0);
       kid->rc = call_submit(c, &kid->call, kid->jobs.data(), kid->jobs.size(), sets, nsets, mode, kid->out.data(),
-                            &kid->st, nullptr, nullptr, (int)d);
+                            &kid->st, nullptr, nullptr, (int)d, pkbits);
       if (kid->rc != BGV_OK && rc == BGV_OK) rc = kid->rc;
       kids.push_back(std::move(kid));
     }
@@ -1494,7 +1757,8 @@ static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv
       if (hi <= lo) continue;
       auto sh = std::make_unique<Shard>();
       sh->job = j;
-      sh->rc = partial_submit(c, &sh->call, sets + jobs[j].first_set + lo, hi - lo, sh->part, sh->codes, (int)d);
+      sh->rc = partial_submit(c, &sh->call, sets + jobs[j].first_set + lo, hi - lo, sh->part, sh->codes, (int)d,
+                              pkbits ? pkbits + jobs[j].first_set + lo : nullptr);
       if (sh->rc != BGV_OK && rc == BGV_OK) rc = sh->rc;
       shards.push_back(std::move(sh));
     }
@@ -1562,18 +1826,28 @@ int bgv_set_split(bgv_ctx* c, uint32_t min_sets) {
 
 int bgv_verify(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
                int32_t* out, bgv_stats* stats) {
+  return bgv_verify_bits(c, jobs, njobs, sets, nsets, nullptr, mode, out, stats);
+}
+
+int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
+                     int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user) {
+  return bgv_verify_bits_async(c, jobs, njobs, sets, nsets, nullptr, mode, out, stats, done, user);
+}
+
+int bgv_verify_bits(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                    const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats) {
   if (!c) return -BGV_E_ARG;
   if (split_wanted(c, nsets)) {
     if (c->closed) return -BGV_E_CLOSED;
     if ((njobs && (!jobs || !out)) || (nsets && !sets)) return -BGV_E_ARG;
     if (mode != BGV_MODE_WORKER && mode != BGV_MODE_PER_JOB) return -BGV_E_ARG;
     if (!split_enter(c)) return -BGV_E_CLOSED;
-    const int rc = verify_split(c, jobs, njobs, sets, nsets, mode, out, stats);
+    const int rc = verify_split(c, jobs, njobs, sets, nsets, pkbits, mode, out, stats);
     split_leave(c);
     return rc;
   }
   Call* call = new Call();
-  int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, nullptr, nullptr);
+  int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, nullptr, nullptr, -1, pkbits);
   if (rc == BGV_OK) {
     std::unique_lock<std::mutex> lk(call->mu);
     call->cv.wait(lk, [call] { return call->finished; });
@@ -1583,8 +1857,9 @@ int bgv_verify(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* set
   return rc;
 }
 
-int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
-                     int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user) {
+int bgv_verify_bits_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                          const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done,
+                          void* user) {
   if (!c) return -BGV_E_ARG;
   if (split_wanted(c, nsets)) {
     // a split call waits for its pieces and combines them: on a thread of its own (big calls
@@ -1594,7 +1869,7 @@ int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_se
     if (mode != BGV_MODE_WORKER && mode != BGV_MODE_PER_JOB) return -BGV_E_ARG;
     if (!split_enter(c)) return -BGV_E_CLOSED;
     std::thread([=] {
-      const int rc = verify_split(c, jobs, njobs, sets, nsets, mode, out, stats);
+      const int rc = verify_split(c, jobs, njobs, sets, nsets, pkbits, mode, out, stats);
       if (done) done(user, rc);
       split_leave(c);
     }).detach();
@@ -1602,7 +1877,7 @@ int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_se
   }
   Call* call = new Call();
   call->owned = true;  // deleted by the dispatcher after done()
-  int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, done, user);
+  int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, done, user, -1, pkbits);
   if (rc != BGV_OK) delete call;
   return rc;
 }
@@ -1900,6 +2175,56 @@ int bgv_aggregate_pubkeys(bgv_ctx* c, const uint32_t* idx, size_t n, uint8_t out
   return BGV_OK;
 }
 
+int bgv_aggregate_committee_bits(bgv_ctx* c, uint32_t id, const uint8_t* bits, uint32_t n_bits, uint8_t out96[96]) {
+  if (!c || !out96 || (n_bits && !bits)) return -BGV_E_ARG;
+  std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+  if (c->closed) return -BGV_E_CLOSED;
+  // one committee set through the call's own checks and layout, then k_pk_agg_bits / pk_sum
+  const uint8_t zero[96] = {0};
+  bgv_set st{};
+  st.sig_len = 96;
+  st.msg = zero;
+  st.sig = zero;
+  const bgv_pkbits pb{id, n_bits, bits};
+  const bgv_job jb{0, 1, 0};
+  Call call;
+  call.setcom.assign(1, SetCommittee{});
+  int32_t code = 2;
+  {
+    std::shared_lock<std::shared_mutex> mlk(c->com_mu);
+    if (host_job_code(c, jb, &st, &code, &pb, &call) != BGV_OK) return -BGV_E_ARG;
+  }
+  if (code != 2) return code;
+  Layout L;
+  std::vector<size_t> todo;
+  layout_call(L, todo, &jb, 1, &st, BGV_MODE_PER_JOB, {2}, call.setcom.data());
+  const uint32_t list = 0;
+  std::lock_guard<std::mutex> lk(c->util_mu);
+  Device& d = c->devs[0];
+  HIPCHK(hipSetDevice(d.id));
+  uint32_t* di = nullptr;
+  uint8_t* dout = nullptr;
+  bgv_dslot* ds = nullptr;
+  void* dagg = nullptr;
+  const bool ok =
+      hipMalloc(reinterpret_cast<void**>(&di), 4 * (L.idx.size() + 1)) == hipSuccess &&
+      hipMalloc(reinterpret_cast<void**>(&dout), 96) == hipSuccess &&
+      hipMalloc(reinterpret_cast<void**>(&ds), sizeof(bgv_dslot)) == hipSuccess &&
+      hipMalloc(&dagg, bgv_g1_point_bytes()) == hipSuccess &&
+      hipMemcpyAsync(di, L.idx.data(), 4 * L.idx.size(), hipMemcpyHostToDevice, d.stream) == hipSuccess &&
+      hipMemcpyAsync(di + L.idx.size(), &list, 4, hipMemcpyHostToDevice, d.stream) == hipSuccess &&
+      hipMemcpyAsync(ds, L.slots.data(), sizeof(bgv_dslot), hipMemcpyHostToDevice, d.stream) == hipSuccess &&
+      bgv_launch_aggregate_bits(ds, di, di + L.idx.size(), !L.com_team.empty(), d.com_dir, d.com_pool, d.cache, dagg,
+                                dout, d.stream) == hipSuccess &&
+      hipMemcpyAsync(out96, dout, 96, hipMemcpyDeviceToHost, d.stream) == hipSuccess;
+  // the stream drains before the buffers (and the host arrays the copies read) go, on every path
+  const bool done = hipStreamSynchronize(d.stream) == hipSuccess;
+  void* bufs[] = {di, dout, ds, dagg};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  return ok && done ? BGV_OK : -BGV_E_DEVICE;
+}
+
 int bgv_hash_to_g2(bgv_ctx* c, const uint8_t* msgs, const uint32_t* lens, size_t n, uint8_t* out192) {
   if (!c || (n && (!lens || !out192))) return -BGV_E_ARG;
   std::shared_lock<std::shared_mutex> clk(c->cache_mu);  // bgv_close frees the devices under the exclusive lock
@@ -2076,8 +2401,10 @@ int bgv_keygen(bgv_ctx* c, const uint8_t* sks, size_t n, int64_t cache_first, ui
     (void)hipFree(dout);
   }
   if (cache_first >= 0) {
+    const size_t old_n = c->n_pubkeys.load();
     for (size_t i = 0; i < n; ++i) c->bad_pk.erase((uint32_t)(cache_first + i));
-    c->n_pubkeys.store(std::max(c->n_pubkeys.load(), (size_t)cache_first + n));
+    c->n_pubkeys.store(std::max(old_n, (size_t)cache_first + n));
+    if ((size_t)cache_first < old_n) return committees_refresh(c, (uint32_t)cache_first, n);
   }
   return BGV_OK;
 }

@@ -15,6 +15,7 @@
 
 #include "../../include/blsgpu.h"
 #include "bgv_layout.h"
+#include "bgv_pk_bits.h"
 
 namespace {
 
@@ -91,6 +92,37 @@ struct uninit_alloc : std::allocator<T> {
   }
 };
 
+// What the host keeps of a live committee for a set's checks (bgv_committee_put): its length,
+// its directory handle on the devices, and whether one of its members is a marked key.
+struct CommitteeInfo {
+  uint32_t handle;
+  uint32_t n;
+  bool bad;
+};
+// A set's pubkeys once its bgv_pkbits passed the checks: handle == BGV_NO_COMMITTEE for a set
+// that brings its own pk_indices / pk_bytes.
+struct SetCommittee {
+  uint32_t handle = BGV_NO_COMMITTEE;
+  uint32_t n = 0;  // members (= n_bits)
+  uint32_t k = 0;  // bits set
+  const uint8_t* bits = nullptr;
+};
+// The argument checks of one committee set (blsgpu.h bgv_verify_bits): 2 and *out filled when it
+// goes to the device, else the code its job gets.  ci: the live committee of pb.committee, or
+// null when the id is unknown or dropped.
+inline int32_t committee_set_check(const CommitteeInfo* ci, const bgv_pkbits& pb, SetCommittee* out) {
+  if (!ci) return -BGV_E_BAD_INDEX;
+  if (pb.n_bits != ci->n) return -BGV_E_ARG;
+  const uint32_t nbytes = (pb.n_bits + 7u) / 8u;
+  if ((pb.n_bits & 7u) && (pb.bits[nbytes - 1] >> (pb.n_bits & 7u))) return -BGV_E_ARG;
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < nbytes; ++i) k += (uint32_t)__builtin_popcount(pb.bits[i]);
+  if (k == 0) return -BGV_E_EMPTY_AGGREGATE;
+  if (ci->bad) return -BGV_E_BAD_INDEX;
+  *out = SetCommittee{ci->handle, ci->n, k, pb.bits};
+  return 2;
+}
+
 // jobs -> slots/groups of one call
 struct Layout {
   std::vector<bgv_dslot, uninit_alloc<bgv_dslot>> slots;
@@ -105,7 +137,21 @@ struct Layout {
   std::vector<uint32_t> idx;             // concatenated pubkey indices
   std::vector<uint8_t> pkb;              // concatenated 96-B pubkey records
   std::vector<uint32_t> uniq;            // first slot of each distinct signing root (hash_to_G2 once)
+  // the committee slots (BGV_SLOT_PK_COMMITTEE) k_pk_agg_bits sums: those whose chosen side has
+  // at most BGV_PK_TEAM_MAX terms (a 16-lane team each), and the others (a wave each)
+  std::vector<uint32_t> com_team, com_wave;
 };
+
+// A call's slot as it stands in a merged super-batch (bgv_api.cpp run_pass1): after slot_base
+// slots, ib words of the index array, pb 96-byte pubkey records and gb groups of earlier calls.
+// A committee slot's run (handle and bit words) lies in the index array like a run of indices.
+inline bgv_dslot rebase_slot(bgv_dslot s, uint32_t slot_base, uint32_t ib, uint32_t pb, uint32_t gb) {
+  s.hsrc += slot_base;
+  if (s.flags & (BGV_SLOT_PK_CACHED | BGV_SLOT_PK_COMMITTEE)) s.pk_off += ib;
+  if (s.flags & BGV_SLOT_PK_BYTES) s.pk_off += pb;
+  if (!(s.flags & BGV_SLOT_PAD)) s.group += gb;
+  return s;
+}
 
 // Which earlier item (slot) shares an item's signing root: the previous item when it has the
 // same root (committees arrive together), else the first item with that root, found by the
@@ -159,7 +205,7 @@ struct Builder {
   void pad_to_wave() {
     while (L.slots.size() % BGV_WAVE) pad();
   }
-  void add(int job, uint32_t set_index, const bgv_set& st, bool first_of_job) {
+  void add(int job, uint32_t set_index, const bgv_set& st, bool first_of_job, const SetCommittee* sc = nullptr) {
     if (!open || L.groups[open_group].n_slots == group_slots()) new_group();
     bgv_dgroup& g = L.groups[open_group];
     if (open_job >= 0 && open_job != job) L.group_shared[open_group] = 1;
@@ -172,7 +218,21 @@ struct Builder {
     s.n_pk = st.n_pk;
     s.sig_len = st.sig_len;
     s.group = open_group;
-    if (st.pk_indices) {
+    if (sc && sc->handle != BGV_NO_COMMITTEE) {
+      // the handle, then the bitfield as 32-bit little-endian words, in the call's index array
+      const bool comp = pkb_use_complement(sc->n, sc->k);
+      s.flags = BGV_SLOT_PK_COMMITTEE | (comp ? BGV_SLOT_PK_COMPLEMENT : 0u);
+      s.n_pk = sc->k;
+      s.pk_off = (uint32_t)L.idx.size();
+      L.idx.push_back(sc->handle);
+      const uint32_t nbytes = (sc->n + 7u) / 8u;
+      for (uint32_t w = 0; w < pkb_nwords(sc->n); ++w) {
+        uint32_t v = 0;
+        for (uint32_t q = 0; q < 4 && 4 * w + q < nbytes; ++q) v |= (uint32_t)sc->bits[4 * w + q] << (8 * q);
+        L.idx.push_back(v);
+      }
+      (pkb_terms(sc->n, sc->k, comp) <= BGV_PK_TEAM_MAX ? L.com_team : L.com_wave).push_back((uint32_t)L.slots.size());
+    } else if (st.pk_indices) {
       s.flags = BGV_SLOT_PK_CACHED;
       s.pk_off = (uint32_t)L.idx.size();
       L.idx.insert(L.idx.end(), st.pk_indices, st.pk_indices + st.n_pk);
@@ -199,12 +259,12 @@ struct Builder {
 // order from slot 0, groups of group_slots() consecutive slots, pads to the wave boundary),
 // with the per-slot records filled by several host threads: the config-5 sweep's 2^20-set
 // job took ~50 ms on one thread.  false: not such a call (the Builder lays it out).
-inline bool layout_one_job_fast(Layout& L, const bgv_job& jb, const bgv_set* sets) {
+inline bool layout_one_job_fast(Layout& L, const bgv_job& jb, const bgv_set* sets, const SetCommittee* sc = nullptr) {
   const uint32_t n = jb.n_sets, gs = group_slots();
   const bgv_set* S = sets + jb.first_set;
   if (n < (1u << 17)) return false;
   for (uint32_t i = 0; i < n; ++i)
-    if (!S[i].pk_indices) return false;
+    if (!S[i].pk_indices || (sc && sc[jb.first_set + i].handle != BGV_NO_COMMITTEE)) return false;
   // signing roots in order, as Builder::add (set i is slot i)
   std::vector<uint32_t> hsrc(n), pk_off(n);
   RootIndex roots;
@@ -264,18 +324,20 @@ inline bool layout_one_job_fast(Layout& L, const bgv_job& jb, const bgv_set* set
 // The first-pass layout of one call.  code[j] == 2 marks the jobs that go to the device (the
 // others were decided by the host's argument checks); they are listed in todo.  Non-batchable
 // jobs own their groups; batchable jobs (worker mode) share.
+// sc (may be null): per set, the committee form of its pubkeys (committee_set_check).
 inline void layout_call(Layout& L, std::vector<size_t>& todo, const bgv_job* jobs, size_t njobs, const bgv_set* sets,
-                        int mode, const std::vector<int32_t>& code) {
+                        int mode, const std::vector<int32_t>& code, const SetCommittee* sc = nullptr) {
   auto shared_job = [&](size_t j) { return mode == BGV_MODE_WORKER && jobs[j].batchable; };
   L.job_groups.resize(njobs);
   L.job_first_slot.assign(njobs, 0);
   Builder B(L);
   for (size_t j = 0; j < njobs; ++j)
     if (code[j] == 2) todo.push_back(j);
-  const bool fast = njobs == 1 && todo.size() == 1 && !shared_job(0) && layout_one_job_fast(L, jobs[0], sets);
+  const bool fast = njobs == 1 && todo.size() == 1 && !shared_job(0) && layout_one_job_fast(L, jobs[0], sets, sc);
   auto add_job = [&](size_t j) {
     for (uint32_t k = 0; k < jobs[j].n_sets; ++k)
-      B.add((int)j, jobs[j].first_set + k, sets[jobs[j].first_set + k], k == 0);
+      B.add((int)j, jobs[j].first_set + k, sets[jobs[j].first_set + k], k == 0,
+            sc ? sc + jobs[j].first_set + k : nullptr);
   };
   for (size_t j : todo) {
     if (shared_job(j) || fast) continue;

@@ -5,6 +5,9 @@
 //   k_pk_agg16 / k_pk_agg  (only when a call holds a set with >= BGV_PK_TREE_MIN cached
 //              keys) a team of 16 lanes per committee-sized set, a whole wavefront per set
 //              above BGV_PK_TEAM_MAX keys, sums its keys with a ds_swizzle/ds_bpermute tree
+//   k_pk_agg_bits  (only when a call holds committee-bitfield sets, BGV_SLOT_PK_COMMITTEE) the
+//              selected members of a device-resident committee, or the unselected ones subtracted
+//              from its total, on a 16-lane team or a whole wave per set (bgv_pk_bits.h)
 //   k_prep_a / k_prep_team   the latency path for small calls (bgv_latency_max): the same
 //              work over two launches with more lanes per set, so the longest chain per
 //              lane roughly halves: (a) one SSWU map + isogeny per lane for u0 and u1, the
@@ -12,6 +15,7 @@
 //              q0 + q1 and r_i * sig_i on 16-lane teams, the subgroup check on one lane
 //   k_prep     (bgv_k_prep_bulk.hip) sig, hash and pk tasks side by side for larger calls
 #include "bgv_k_lat.h"
+#include "bgv_pk_bits.h"
 #include "bgv_team_dev.h"
 #include "bgv_tcurve.h"
 #include "bgv_tg1.h"
@@ -61,8 +65,80 @@ struct tc_dev_engine {
 #define BGV_WPE_AGG 2
 #endif
 
-extern "C" {
+// Committee-bitfield sets (bgv_pk_bits.h).  One team of T lanes (16: four slots per wave, 64: the
+// wave) sums the chosen side of one slot: lane l gathers the selected members of rank l, l + T,
+// ... (direct mode: bit set; complement mode: bit clear), found from the per-word popcount
+// prefix, so every lane of a team does the same number of additions whatever the pattern.  Every
+// lane reads the same bit word at a time (one broadcast fetch) and the member table through it;
+// each key is gathered one addition ahead of its use.  words == nullptr selects every member
+// (the committee's total, k_committee_total).  Then the butterfly inside the team; complement
+// mode returns total + (-sum).  The additions are the complete ones (jac_add_aff with its
+// doubling branch, jac_add), so members that cancel, an infinity total and an infinity result
+// take no special case.  Every lane of the wave must reach the exchanges: an idle team (act
+// false) carries infinity through them.
+static_assert(sizeof(g1_jac) == sizeof(bgv_dcommittee::total), "bgv_dcommittee keeps a Jacobian G1 point");
+template <int T>
+__device__ __forceinline__ g1_jac pk_bits_sum(bool act, uint32_t l, const uint32_t* __restrict__ words,
+                                              const uint32_t* __restrict__ members, uint32_t n, bool comp,
+                                              const g1_aff* __restrict__ cache) {
+  g1_jac acc = jac_infinity<fp_t>();
+  if (act) {
+    pkb_cursor c = pkb_begin(l);
+    uint32_t pos;
+    if (pkb_next(c, words, n, comp, T, &pos)) {
+      acc = jac_from_aff(cache[members[pos]]);
+      bool have = pkb_next(c, words, n, comp, T, &pos);
+      g1_aff cur = cache[members[have ? pos : 0]];
+      while (have) {
+        uint32_t pn;
+        const bool hn = pkb_next(c, words, n, comp, T, &pn);
+        const g1_aff nxt = cache[members[hn ? pn : pos]];
+        acc = jac_add_aff(acc, cur);
+        cur = nxt;
+        pos = hn ? pn : pos;
+        have = hn;
+      }
+    }
+  }
+  if constexpr (T == 64) {
+    acc = jac_add(acc, point_xor<32>(acc));
+    acc = jac_add(acc, point_xor<16>(acc));
+  }
+  acc = jac_add(acc, point_xor<8>(acc));
+  acc = jac_add(acc, point_xor<4>(acc));
+  acc = jac_add(acc, point_xor<2>(acc));
+  acc = jac_add(acc, point_xor<1>(acc));
+  return acc;
+}
 
+// pk_agg[s] of committee slot s on a team of T lanes (lane l of it); act false: an idle team
+template <int T>
+__device__ __forceinline__ void pk_bits_slot(bool act, uint32_t s, uint32_t l, const bgv_dslot* __restrict__ slots,
+                                             const uint32_t* __restrict__ pk_idx,
+                                             const bgv_dcommittee* __restrict__ dir,
+                                             const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache,
+                                             g1_jac* __restrict__ pk_agg, bool writer) {
+  const uint32_t* words = nullptr;
+  const uint32_t* members = nullptr;
+  const bgv_dcommittee* cm = nullptr;
+  uint32_t n = 0;
+  bool comp = false;
+  if (act) {
+    const bgv_dslot& d = slots[s];
+    cm = dir + pk_idx[d.pk_off];
+    words = pk_idx + d.pk_off + 1;
+    members = pool + cm->off;
+    n = cm->n;
+    comp = (d.flags & BGV_SLOT_PK_COMPLEMENT) != 0;
+  }
+  g1_jac acc = pk_bits_sum<T>(act, l, words, members, n, comp, cache);
+  if (act && writer) {
+    if (comp) acc = jac_add(*reinterpret_cast<const g1_jac*>(cm->total), jac_neg(acc));
+    pk_agg[s] = acc;
+  }
+}
+
+extern "C" {
 
 // Pubkey aggregation of many-key sets as a wavefront tree (one wave per slot): lane l
 // sums the set's cached keys l, l + 64, ... with mixed additions (coalesced gathers),
@@ -140,6 +216,62 @@ __device__ __forceinline__ void pk_agg_one(const bgv_dslot* __restrict__ slots, 
   acc = jac_add(acc, point_xor<2>(acc));
   acc = jac_add(acc, point_xor<1>(acc));
   if (threadIdx.x == 0) pk_agg[s] = acc;
+}
+
+// com: the batch's committee slots, nteam of them on 16-lane teams (four per block), then nwave
+// on a wave each.  One wave per SIMD: the cursor, the prefetched key and the sum fit the
+// registers (at two waves per SIMD the compiler spills 354 VGPRs to scratch).
+#ifndef BGV_WPE_BITS
+#define BGV_WPE_BITS 1
+#endif
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BGV_WPE_BITS, BGV_WPE_BITS)))
+k_pk_agg_bits(const bgv_dslot* __restrict__ slots, const uint32_t* __restrict__ com, uint32_t nteam, uint32_t nwave,
+              const uint32_t* __restrict__ pk_idx, const bgv_dcommittee* __restrict__ dir,
+              const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache, g1_jac* __restrict__ pk_agg) {
+  const uint32_t nb_team = (nteam + 3) / 4;
+  if (blockIdx.x < nb_team) {
+    const uint32_t q = blockIdx.x * 4 + threadIdx.x / 16, l = threadIdx.x % 16;
+    const bool act = q < nteam;
+    pk_bits_slot<16>(act, act ? com[q] : 0u, l, slots, pk_idx, dir, pool, cache, pk_agg, l == 0);
+  } else {
+    const uint32_t q = nteam + (blockIdx.x - nb_team);
+    const bool act = q < nteam + nwave;
+    pk_bits_slot<64>(act, act ? com[q] : 0u, threadIdx.x, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
+  }
+}
+
+// One committee slot on a whole 64-lane block (k_prep_wide's pubkey plane), where the block has
+// nothing else to do: the shorter chain of additions decides.  A 16-lane team (the four teams
+// of the block repeat each other, as pk_agg_one's do) runs ceil(m / 16) + 4 additions per lane
+// for m terms, the whole wave ceil(m / 64) + 6: the wave from BGV_PK_ONE_WAVE_MIN terms on
+// (m = 49: 8 against 7).  The high-participation sets this path serves have a few terms.  Out of line: k_prep_wide's other planes and its index-set path keep the code they
+// had without it.
+#define BGV_PK_ONE_WAVE_MIN 49
+__device__ __noinline__ void pk_bits_one(const bgv_dslot* __restrict__ slots, uint32_t s,
+                                            const uint32_t* __restrict__ pk_idx,
+                                            const bgv_dcommittee* __restrict__ dir,
+                                            const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache,
+                                            g1_jac* __restrict__ pk_agg) {
+  const bgv_dslot& d = slots[s];
+  if ((d.flags & BGV_SLOT_PAD) || !(d.flags & BGV_SLOT_PK_COMMITTEE)) return;  // uniform over the block
+  const uint32_t n = dir[pk_idx[d.pk_off]].n;
+  if (pkb_terms(n, d.n_pk, (d.flags & BGV_SLOT_PK_COMPLEMENT) != 0) < BGV_PK_ONE_WAVE_MIN)
+    pk_bits_slot<16>(true, s, threadIdx.x % 16, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
+  else
+    pk_bits_slot<64>(true, s, threadIdx.x, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
+}
+
+// The pubkey sums of the committees listed in handles (one wave each) into their directory
+// entries: k_pk_agg_bits' body with every bit set, direct mode (bgv_committee_put, and after a
+// bgv_pubkeys_put over members of live committees).
+__global__ void __launch_bounds__(64) k_committee_total(bgv_dcommittee* __restrict__ dir,
+                                                        const uint32_t* __restrict__ handles, uint32_t nh,
+                                                        const uint32_t* __restrict__ pool,
+                                                        const g1_aff* __restrict__ cache) {
+  if (blockIdx.x >= nh) return;
+  bgv_dcommittee* cm = dir + handles[blockIdx.x];
+  const g1_jac acc = pk_bits_sum<64>(true, threadIdx.x, nullptr, pool + cm->off, cm->n, false, cache);
+  if (threadIdx.x == 0) *reinterpret_cast<g1_jac*>(cm->total) = acc;
 }
 
 __global__ void __launch_bounds__(64) k_pk_agg(const bgv_dslot* __restrict__ slots, uint32_t nslots,
@@ -269,7 +401,9 @@ __global__ void __launch_bounds__(64) k_prep_wide(const bgv_dslot* __restrict__ 
                                                   const uint32_t* __restrict__ pk_idx,
                                                   const g1_aff* __restrict__ cache, const uint8_t* __restrict__ pk_bytes,
                                                   g1_jac* __restrict__ rpk, int32_t* __restrict__ pk_status,
-                                                  g1_jac* __restrict__ pk_agg) {
+                                                  g1_jac* __restrict__ pk_agg,
+                                                  const bgv_dcommittee* __restrict__ com_dir,
+                                                  const uint32_t* __restrict__ com_pool) {
   static_assert(TG1_TABLE_BYTES <= TCP_TABLE_BYTES && TG1_NSLOT <= TCP_NSLOT, "plane 3 reuses the G2 buffers");
   __shared__ uint8_t prog[TCP_TABLE_BYTES];
   __shared__ fp_t S[TCP_NSLOT];
@@ -281,6 +415,7 @@ __global__ void __launch_bounds__(64) k_prep_wide(const bgv_dslot* __restrict__ 
     // programs (bgv_tg1.h) as rounds, concurrently with the other planes' G2 programs
     const uint32_t s = blockIdx.x;
     if (pk_agg) pk_agg_one(slots, s, pk_idx, cache, pk_agg);
+    if (pk_agg) pk_bits_one(slots, s, pk_idx, com_dir, com_pool, cache, pk_agg);  // a committee-bitfield set
     if (threadIdx.x == 0) {
       g1_jac acc;
       const bool go = task_pk_sum(s, slots, pk_idx, cache, pk_bytes, pk_status, pk_agg, &acc);
@@ -412,16 +547,22 @@ hipError_t bgv_launch_prep(const bgv_dev_batch& b, const bgv_streams& s) {
   BGV_MARK(0);
   // k_pk_agg only when some set is large enough; otherwise k_prep sums serially (null pk_agg)
   const bool tree = b.max_npk >= BGV_PK_TREE_MIN;
+  const uint32_t ncom = b.ncom_team + b.ncom_wave;  // committee-bitfield slots: their sums are in pk_agg too
+  const bool agg = tree || ncom > 0;
   const bool wide = bgv_use_latency(b, n + b.ngroups) && n <= BGV_PREP_WIDE_MAX;
   if (wide) {
     const g1_aff* cache = reinterpret_cast<const g1_aff*>(b.cache_opaque);
     const hipError_t e = bgv_launch_prep_wave(b, s.main);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_prep_wide, dim3(n, 4), dim3(64), 0, s.main, b.slots, n, b.h, b.f, b.rsig, b.sig_status,
-                       b.pk_idx, cache, b.pk_bytes, b.rpk, b.pk_status, tree ? b.pk_agg : nullptr);
+                       b.pk_idx, cache, b.pk_bytes, b.rpk, b.pk_status, agg ? b.pk_agg : nullptr, b.com_dir, b.com_pool);
     BGV_MARK(1);
     return hipGetLastError();
   }
+  if (ncom)
+    hipLaunchKernelGGL(k_pk_agg_bits, dim3(nblk(b.ncom_team, 4) + b.ncom_wave), dim3(64), 0, s.main, b.slots, b.com,
+                       b.ncom_team, b.ncom_wave, b.pk_idx, b.com_dir, b.com_pool,
+                       reinterpret_cast<const g1_aff*>(b.cache_opaque), b.pk_agg);
   if (tree)
     hipLaunchKernelGGL(k_pk_agg16, dim3(nblk(n, 4)), dim3(64), 0, s.main, b.slots, n, b.pk_idx,
                        reinterpret_cast<const g1_aff*>(b.cache_opaque), b.pk_agg);
@@ -431,11 +572,11 @@ hipError_t bgv_launch_prep(const bgv_dev_batch& b, const bgv_streams& s) {
   if (bgv_use_latency(b, n + b.ngroups)) {
     hipLaunchKernelGGL(k_prep_a, dim3(nblk(n, 64), 4), dim3(64), 0, s.main, b.slots, n, b.h, b.f, b.sig_status,
                        b.pk_idx, reinterpret_cast<const g1_aff*>(b.cache_opaque), b.pk_bytes, b.rpk, b.pk_status,
-                       tree ? b.pk_agg : nullptr);
+                       agg ? b.pk_agg : nullptr);
     hipLaunchKernelGGL(k_prep_team, dim3(nblk(n, BGV_FINAL_TEAMS), 3), dim3(64), 0, s.main, b.slots, n, b.h, b.f,
                        b.rsig, b.sig_status);
   } else {
-    const hipError_t e = bgv_launch_prep_bulk(b, s, tree);
+    const hipError_t e = bgv_launch_prep_bulk(b, s, agg);
     if (e != hipSuccess) return e;
   }
   BGV_MARK(1);
@@ -451,5 +592,28 @@ hipError_t bgv_launch_aggregate(const bgv_dslot* slot, const uint32_t* idx, uint
   if (tree && n <= BGV_PK_TEAM_MAX) hipLaunchKernelGGL(k_pk_agg16, dim3(1), dim3(64), 0, st, slot, 1u, idx, c, a);
   if (tree && n > BGV_PK_TEAM_MAX) hipLaunchKernelGGL(k_pk_agg, dim3(1), dim3(64), 0, st, slot, 1u, idx, c, a);
   hipLaunchKernelGGL(k_pk_sum_out, dim3(1), dim3(64), 0, st, slot, idx, c, tree ? a : nullptr, out96);
+  return hipGetLastError();
+}
+
+// The aggregate of one committee slot through k_pk_agg_bits.  slot: one device bgv_dslot
+// {PK_COMMITTEE [| PK_COMPLEMENT], n_pk = bits set, pk_off = 0}; idx: the handle, then the bit
+// words; list: one zero word (the slot's id); team: the chosen side has at most
+// BGV_PK_TEAM_MAX terms; agg: one g1_jac of scratch
+hipError_t bgv_launch_aggregate_bits(const bgv_dslot* slot, const uint32_t* idx, const uint32_t* list, bool team,
+                                     const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
+                                     void* agg, uint8_t* out96, hipStream_t st) {
+  const g1_aff* c = reinterpret_cast<const g1_aff*>(cache);
+  g1_jac* a = reinterpret_cast<g1_jac*>(agg);
+  hipLaunchKernelGGL(k_pk_agg_bits, dim3(1), dim3(64), 0, st, slot, list, team ? 1u : 0u, team ? 0u : 1u, idx, dir, pool,
+                     c, a);
+  hipLaunchKernelGGL(k_pk_sum_out, dim3(1), dim3(64), 0, st, slot, idx, c, a, out96);
+  return hipGetLastError();
+}
+
+hipError_t bgv_launch_committee_totals(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, const uint32_t* pool,
+                                       const bgv_cache_entry* cache, hipStream_t st) {
+  if (nh == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_committee_total, dim3(nh), dim3(64), 0, st, dir, handles, nh, pool,
+                     reinterpret_cast<const g1_aff*>(cache));
   return hipGetLastError();
 }

@@ -46,12 +46,13 @@ static __device__ __noinline__ void task_hash(uint32_t s, const bgv_dslot* __res
 }
 
 // Sum of one set's pubkeys (PublicKey.aggregate, chain/bls/utils.ts:5-16): the k_pk_agg
-// tree sum when the set went through it, else serial mixed additions of cached keys or of
+// tree sum when the set went through it, k_pk_agg_bits' sum for a committee-bitfield set, else serial mixed additions of cached keys or of
 // 96-byte records (decoded like blst's PublicKey.fromBytes, bls_curve.h g1_deserialize).
 // *st receives the first record's decode error, if any.
 __device__ __noinline__ static g1_jac pk_sum(const bgv_dslot& d, const uint32_t* __restrict__ pk_idx,
                                       const g1_aff* __restrict__ cache, const uint8_t* __restrict__ pk_bytes,
                                       const g1_jac* __restrict__ pk_agg, uint32_t s, int32_t* st) {
+  if (d.flags & BGV_SLOT_PK_COMMITTEE) return pk_agg[s];  // summed by k_pk_agg_bits (bgv_k_prep.hip)
   g1_jac acc = jac_infinity<fp_t>();
   const bool cached = (d.flags & BGV_SLOT_PK_CACHED) != 0;
   const bool tree = pk_agg != nullptr && cached && d.n_pk >= BGV_PK_TREE_MIN;  // summed by k_pk_agg

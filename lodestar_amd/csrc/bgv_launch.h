@@ -39,6 +39,13 @@ struct bgv_dev_batch {
   const uint32_t* pk_idx;
   const bgv_cache_entry* cache_opaque;
   const uint8_t* pk_bytes;
+  // committee-bitfield slots (BGV_SLOT_PK_COMMITTEE): their ids -- ncom_team on 16-lane teams,
+  // then ncom_wave on a wave each (k_pk_agg_bits) -- and the device's committee directory and
+  // index pool (bgv_committee_put)
+  const uint32_t* com;
+  uint32_t ncom_team, ncom_wave;
+  const bgv_dcommittee* com_dir;
+  const uint32_t* com_pool;
   // carved per-slot / per-group scratch
   jac_t<fp2_t>* rsig;  // r_i * sig_i (Jacobian), summed per group by k_final
   jac_t<fp2_t>* h;     // H(m_i), Jacobian
@@ -109,6 +116,12 @@ hipError_t bgv_launch_cache_put(const uint8_t* keys, uint32_t n, int fmt, bgv_ca
                                 hipStream_t st);
 hipError_t bgv_launch_aggregate(const bgv_dslot* slot, const uint32_t* idx, uint32_t n, const bgv_cache_entry* cache,
                                 void* agg, uint8_t* out96, hipStream_t st);
+hipError_t bgv_launch_aggregate_bits(const bgv_dslot* slot, const uint32_t* idx, const uint32_t* list, bool team,
+                                     const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
+                                     void* agg, uint8_t* out96, hipStream_t st);
+// the pubkey sums of the committees in handles into their directory entries
+hipError_t bgv_launch_committee_totals(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, const uint32_t* pool,
+                                       const bgv_cache_entry* cache, hipStream_t st);
 size_t bgv_g1_point_bytes();
 hipError_t bgv_launch_debug_out(const bgv_dev_batch& b, uint8_t* out_h192, uint8_t* out_f576, hipStream_t st);
 hipError_t bgv_launch_hash(const uint8_t* msgs, const uint32_t* offs, const uint32_t* lens, uint32_t n,

@@ -14,6 +14,14 @@ enum {
   BGV_SLOT_PAD = 1u,        // empty lane
   BGV_SLOT_PK_CACHED = 2u,  // pubkeys are validator indices into the device cache
   BGV_SLOT_PK_BYTES = 4u,   // pubkeys are 96-byte uncompressed records uploaded with the call
+  // pubkeys are the members of a device-resident committee selected by a bitfield
+  // (bgv_committee_put, bgv_verify_bits): at pk_off in the index array the committee's
+  // directory handle, then ceil(n / 32) little-endian words of the bitfield; n_pk counts the set
+  // bits.  k_pk_agg_bits sums the slot into pk_agg (bgv_pk_bits.h)
+  BGV_SLOT_PK_COMMITTEE = 8u,
+  // with BGV_SLOT_PK_COMMITTEE: the members whose bit is CLEAR are summed and subtracted from the
+  // committee's total (fewer additions when more than half take part)
+  BGV_SLOT_PK_COMPLEMENT = 16u,
 };
 
 // Per-slot input record (160 B, 16-B aligned).
@@ -28,6 +36,14 @@ struct bgv_dslot {
                     // signing root (its own index for that first slot and for pads)
   uint8_t msg[32];  // signing root
   uint8_t sig[96];  // compressed G2 signature (untrusted wire bytes)
+};
+
+// One device-resident committee (the directory entry a BGV_SLOT_PK_COMMITTEE slot names by its
+// handle): n validator indices at pool[off ..] and their pubkey sum.
+struct bgv_dcommittee {
+  uint32_t off;
+  uint32_t n;
+  uint64_t total[21];  // Jacobian G1 point (x, y, z; Montgomery form), may be infinity
 };
 
 // Per-slot status codes written by the kernels (BLST numbering, see blsgpu.h)

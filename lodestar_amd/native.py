@@ -34,6 +34,8 @@ PATH_BULK = 1
 PATH_LATENCY = 2
 PK_COMPRESSED = 48
 PK_UNCOMPRESSED = 96
+MAX_COMMITTEES = 16384
+NO_COMMITTEE = 0xFFFFFFFF
 
 EXPORTED_SYMBOLS = [
     "bgv_init", "bgv_close", "bgv_destroy", "bgv_pubkeys_put", "bgv_pubkeys_count", "bgv_verify",
@@ -41,6 +43,8 @@ EXPORTED_SYMBOLS = [
     "bgv_set_rng_seed", "bgv_strerror", "bgv_device_count", "bgv_profile",
     "bgv_pubkeys_validate", "bgv_aggregate_signatures", "bgv_deposits_verify", "bgv_set_batching",
     "bgv_verify_partial", "bgv_final_verify", "bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split",
+    "bgv_committee_put", "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
+    "bgv_aggregate_committee_bits",
 ]
 
 
@@ -53,6 +57,10 @@ class BgvSet(ctypes.Structure):
         ("msg", ctypes.c_void_p),
         ("sig", ctypes.c_void_p),
     ]
+
+
+class BgvPkBits(ctypes.Structure):
+    _fields_ = [("committee", ctypes.c_uint32), ("n_bits", ctypes.c_uint32), ("bits", ctypes.c_void_p)]
 
 
 class BgvJob(ctypes.Structure):
@@ -114,9 +122,16 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_pubkeys_validate": ([P, P, SZ, P, P], ctypes.c_int),
             "bgv_aggregate_signatures": ([P, P, P, P, SZ, P, P], ctypes.c_int),
             "bgv_deposits_verify": ([P, P, P, P, SZ, P], ctypes.c_int),
+            "bgv_committee_put": ([P, U32, P, SZ], ctypes.c_int),
+            "bgv_committee_drop": ([P, U32], ctypes.c_int),
+            "bgv_verify_bits": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P], ctypes.c_int),
+            "bgv_verify_bits_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, DONE_FN, P], ctypes.c_int),
+            "bgv_aggregate_committee_bits": ([P, U32, P, U32, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
-            if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split") and path != os.path.join(HERE, "libblsgpu.so") and \
+            if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
+                        "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
+                        "bgv_aggregate_committee_bits") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -223,6 +238,23 @@ class Context:
 
     def pubkeys_count(self) -> int:
         return self.lib.bgv_pubkeys_count(self._h)
+
+    # --- device-resident committees (bgv_committee_put) -----------------------
+    def committee_put(self, committee_id: int, indices: Sequence[int]):
+        """Store a committee's validator indices and their pubkey sum on the device(s) under
+        committee_id; sets then name (committee, bitfield): SetSpec(..., committee=, bits=, n_bits=)."""
+        arr = (ctypes.c_uint32 * max(1, len(indices)))(*indices)
+        _check(self.lib.bgv_committee_put(self._h, committee_id, arr, len(indices)))
+
+    def committee_drop(self, committee_id: int):
+        _check(self.lib.bgv_committee_drop(self._h, committee_id))
+
+    def aggregate_committee_bits(self, committee_id: int, bits: bytes, n_bits: int) -> bytes:
+        """The aggregate of the committee members whose bit is set (SSZ bit order), 96 B
+        uncompressed, through the verify path's kernel (bgv_aggregate_committee_bits)."""
+        out = ctypes.create_string_buffer(96)
+        _check(self.lib.bgv_aggregate_committee_bits(self._h, committee_id, _buf(bits), n_bits, out))
+        return out.raw
 
     def keygen(self, sks: bytes, cache_first: int = -1, want_pubkeys: bool = True) -> bytes:
         n = len(sks) // 32
@@ -332,30 +364,48 @@ class Context:
     def verify_jobs(self, jobs, mode: int = MODE_WORKER, stats: Optional[BgvStats] = None) -> List[int]:
         """jobs: list of (sets, batchable) with sets = list of SetSpec.  Returns the
         per-job codes (1 valid, 0 invalid, -code error)."""
-        packed = PackedCall(jobs)
-        out = (ctypes.c_int32 * max(1, len(jobs)))()
-        rc = self.lib.bgv_verify(self._h, packed.jobs, len(jobs), packed.sets, packed.nsets, mode, out,
-                                 ctypes.byref(stats) if stats is not None else None)
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        njobs = len(packed.jobs_in)
+        out = (ctypes.c_int32 * max(1, njobs))()
+        st = ctypes.byref(stats) if stats is not None else None
+        if packed.pkbits is not None:  # some set names (committee, bitfield)
+            rc = self.lib.bgv_verify_bits(self._h, packed.jobs, njobs, packed.sets, packed.nsets, packed.pkbits,
+                                          mode, out, st)
+        else:
+            rc = self.lib.bgv_verify(self._h, packed.jobs, njobs, packed.sets, packed.nsets, mode, out, st)
         _check(rc)
-        return list(out[:len(jobs)])
+        return list(out[:njobs])
 
 
 class SetSpec:
-    """One ISignatureSet in C-ABI terms: pubkeys by cache index or 96-B bytes."""
+    """One ISignatureSet in C-ABI terms: pubkeys by cache index, as 96-B bytes, or as the members
+    of a device-resident committee (Context.committee_put) selected by an SSZ bitfield of n_bits
+    bits (member k takes part iff (bits[k >> 3] >> (k & 7)) & 1)."""
 
-    __slots__ = ("pk_indices", "pk_bytes", "msg", "sig")
+    __slots__ = ("pk_indices", "pk_bytes", "msg", "sig", "committee", "bits", "n_bits")
 
     def __init__(self, msg: bytes, sig: bytes, pk_indices: Optional[Sequence[int]] = None,
-                 pk_bytes: Optional[Sequence[bytes]] = None):
+                 pk_bytes: Optional[Sequence[bytes]] = None, committee: Optional[int] = None,
+                 bits: Optional[bytes] = None, n_bits: Optional[int] = None):
         self.pk_indices = list(pk_indices) if pk_indices is not None else None
         self.pk_bytes = list(pk_bytes) if pk_bytes is not None else None
         self.msg = bytes(msg)
         self.sig = bytes(sig)
-        if (self.pk_indices is None) == (self.pk_bytes is None):
+        self.committee = committee
+        self.bits = bytes(bits) if bits is not None else None
+        self.n_bits = n_bits
+        if committee is not None:
+            if pk_indices is not None or pk_bytes is not None or bits is None or n_bits is None:
+                raise ValueError("a committee set takes bits and n_bits, and no pk_indices / pk_bytes")
+            if len(self.bits) != (n_bits + 7) // 8:
+                raise ValueError("bits must hold ceil(n_bits / 8) bytes")
+        elif (self.pk_indices is None) == (self.pk_bytes is None):
             raise ValueError("exactly one of pk_indices / pk_bytes")
 
     @property
     def n_pk(self):
+        if self.committee is not None:
+            return sum(bin(b).count("1") for b in self.bits)
         return len(self.pk_indices) if self.pk_indices is not None else len(self.pk_bytes)
 
 
@@ -401,9 +451,16 @@ class PackedCall:
             jarr[j].n_sets = len(sets)
             jarr[j].batchable = 1 if batchable else 0
             all_sets.extend(sets)
+        self.jobs_in = jobs
         self.nsets = len(all_sets)
         sarr = (BgvSet * max(1, len(all_sets)))()
         keep = []
+        # the bgv_pkbits array beside the sets, only when some set names a committee
+        self.pkbits = None
+        if any(s.committee is not None for s in all_sets):
+            self.pkbits = (BgvPkBits * max(1, len(all_sets)))()
+            for i in range(len(all_sets)):
+                self.pkbits[i].committee = NO_COMMITTEE
         for i, s in enumerate(all_sets):
             msg = ctypes.create_string_buffer(s.msg, 32) if len(s.msg) == 32 else None
             if msg is None:
@@ -414,7 +471,13 @@ class PackedCall:
             sarr[i].sig_len = len(s.sig)
             sarr[i].msg = ctypes.addressof(msg)
             sarr[i].sig = ctypes.addressof(sig)
-            if s.pk_indices is not None:
+            if s.committee is not None:
+                bits = _buf(s.bits)
+                keep.append(bits)
+                self.pkbits[i].committee = s.committee
+                self.pkbits[i].n_bits = s.n_bits
+                self.pkbits[i].bits = ctypes.addressof(bits)
+            elif s.pk_indices is not None:
                 idx = (ctypes.c_uint32 * max(1, len(s.pk_indices)))(*s.pk_indices)
                 keep.append(idx)
                 sarr[i].pk_indices = ctypes.addressof(idx)

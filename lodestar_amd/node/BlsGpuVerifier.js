@@ -34,7 +34,10 @@ const MAX_SIGNATURE_SETS_PER_JOB = 128; // index.ts:39
 const MAX_BUFFERED_SIGS = 63;
 const MAX_BUFFER_WAIT_MS = 1;
 
-const SignatureSetType = {single: "single", aggregate: "aggregate"};
+// committee: not in the reference -- an aggregate as the beacon node holds it before
+// bits.intersectValues(committeeIndices): a committee stored on the device (committeePut) and
+// the participation bitfield
+const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee"};
 const PUBKEY_RUN = 8192;
 // include/blsgpu.h: BGV_BLST_* decode statuses are 1..19 (library codes start at 20)
 const isBlstDecodeCode = (code) => typeof code === "number" && code <= -1 && code >= -19;
@@ -78,7 +81,25 @@ function chunkifyMaximizeChunkSize(arr, minPerChunk) {
 /** chain/bls/utils.ts:18-26 */
 function getAggregatedPubkeysCount(sets) {
   let n = 0;
-  for (const s of sets) if (s.type === SignatureSetType.aggregate) n += s.pubkeys.length;
+  for (const s of sets) {
+    if (s.type === SignatureSetType.aggregate) n += s.pubkeys.length;
+    else if (s.type === SignatureSetType.committee) n += countBits(committeeBits(s).bits);
+  }
+  return n;
+}
+
+// The bitfield of a committee set: `bits` is a Uint8Array of ceil(nBits / 8) bytes in SSZ bit
+// order (member k takes part iff (bits[k >> 3] >> (k & 7)) & 1) with `nBits` beside it, or a
+// BitArray ({uint8Array, bitLen}: an attestation's aggregationBits, a syncCommitteeBits).
+function committeeBits(s) {
+  const bits = s.bits.uint8Array || s.bits;
+  const nBits = s.nBits !== undefined ? s.nBits : s.bits.bitLen !== undefined ? s.bits.bitLen : 8 * bits.length;
+  return {bits, nBits};
+}
+
+function countBits(bytes) {
+  let n = 0;
+  for (let b of bytes) for (; b; b &= b - 1) n++;
   return n;
 }
 
@@ -95,6 +116,10 @@ function uncompressed(pk) {
 }
 
 function toNativeSet(s) {
+  if (s.type === SignatureSetType.committee) {
+    const {bits, nBits} = committeeBits(s);
+    return {committee: s.committee, bits, nBits, msg: s.signingRoot, sig: s.signature};
+  }
   let pks;
   if (s.type === SignatureSetType.single) pks = [s.pubkey];
   else if (s.type === SignatureSetType.aggregate) pks = s.pubkeys;
@@ -233,6 +258,21 @@ class BlsGpuVerifier {
     );
     if (results.length === 0) throw Error("Empty results array");
     return results.every((v) => v === true);
+  }
+
+  /**
+   * A committee onto the device(s) under `id` (0..16383): its validator indices and their pubkey
+   * sum (INTEGRATION.md §2c).  Sets of type "committee" then name it with a bitfield.  The
+   * queued pubkeys go first, so a committee of just-added validators finds its keys.
+   */
+  async committeePut(id, indices) {
+    await this.flushPubkeys();
+    addon.committeePut(this.ctx, id, indices instanceof Uint32Array ? indices : Uint32Array.from(indices));
+  }
+
+  /** Frees the id at once; calls already queued finish on the committee they named. */
+  committeeDrop(id) {
+    addon.committeeDrop(this.ctx, id);
   }
 
   // index.ts:176-197.  Idempotent; device calls already in flight complete (the library

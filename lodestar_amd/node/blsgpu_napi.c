@@ -108,6 +108,8 @@ typedef struct {
   bgv_job* jobs;
   size_t njobs;
   bgv_set* sets;
+  bgv_pkbits* pkbits; /* beside sets; handed to the library only when a set names a committee */
+  int any_committee;
   size_t nsets;
   int mode;
   int32_t* codes;
@@ -352,6 +354,58 @@ static napi_value js_aggregate_pubkeys(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* committeePut(ctx, id, indices: Uint32Array): the committee's validator indices and their pubkey
+ * sum onto the device(s) under id (bgv_committee_put); sets then name {committee, bits, nBits}.
+ * committeeDrop(ctx, id) frees the id. */
+static napi_value js_committee_put(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t id = 0;
+  uint8_t* idx;
+  size_t len;
+  if (argc < 3 || napi_get_value_uint32(env, argv[1], &id) != napi_ok || get_bytes(env, argv[2], &idx, &len) ||
+      len % 4)
+    return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_committee_put(ctx, id, (const uint32_t*)idx, len / 4);
+  if (rc) return throw_code(env, rc);
+  return NULL;
+}
+
+static napi_value js_committee_drop(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t id = 0;
+  if (argc < 2 || napi_get_value_uint32(env, argv[1], &id) != napi_ok) return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_committee_drop(ctx, id);
+  if (rc) return throw_code(env, rc);
+  return NULL;
+}
+
+/* aggregateCommitteeBits(ctx, id, bits: Uint8Array, nBits) -> Uint8Array(96): the aggregate of the
+ * committee members whose bit is set, through the verify path's kernel (parity hook). */
+static napi_value js_aggregate_committee_bits(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t id = 0, nbits = 0;
+  uint8_t* bits;
+  size_t len;
+  if (argc < 4 || napi_get_value_uint32(env, argv[1], &id) != napi_ok || get_bytes(env, argv[2], &bits, &len) ||
+      napi_get_value_uint32(env, argv[3], &nbits) != napi_ok || len != ((size_t)nbits + 7) / 8)
+    return throw_code(env, -BGV_E_ARG);
+  void* dst;
+  napi_value out = new_bytes(env, 96, &dst);
+  if (!out) return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_aggregate_committee_bits(ctx, id, bits, nbits, (uint8_t*)dst);
+  if (rc) return throw_code(env, rc);
+  return out;
+}
+
 /* hashToG2(ctx, msg: Uint8Array) -> Uint8Array(192) uncompressed (x.c1|x.c0|y.c1|y.c0) */
 static napi_value js_hash_to_g2(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -489,6 +543,7 @@ static void free_req(napi_env env, verify_req* r) {
   free(r->refs);
   free(r->jobs);
   free(r->sets);
+  free(r->pkbits);
   free(r->codes);
   free(r);
 }
@@ -605,6 +660,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   r->codes = (int32_t*)calloc(njobs ? njobs : 1, sizeof(int32_t));
   size_t cap = 64;
   r->sets = (bgv_set*)calloc(cap, sizeof(bgv_set));
+  r->pkbits = (bgv_pkbits*)calloc(cap, sizeof(bgv_pkbits));
   size_t refcap = 256;
   r->refs = (napi_ref*)calloc(refcap, sizeof(napi_ref));
   for (uint32_t j = 0; j < njobs; ++j) {
@@ -623,6 +679,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
       if (r->nsets == cap) {
         cap *= 2;
         r->sets = (bgv_set*)realloc(r->sets, cap * sizeof(bgv_set));
+        r->pkbits = (bgv_pkbits*)realloc(r->pkbits, cap * sizeof(bgv_pkbits));
       }
       if (r->nrefs + 4 > refcap) {
         refcap *= 2;
@@ -630,22 +687,43 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
       }
       napi_value s, pk, msg, sig;
       napi_get_element(env, sets, k, &s);
-      /* pkIndices (validator indices into the device cache) or pkBytes (n x 96-B uncompressed) */
-      bool by_index = false;
+      /* pkIndices (validator indices into the device cache), pkBytes (n x 96-B uncompressed), or
+       * committee + bits + nBits (the members of a committee stored with committeePut whose bit is
+       * set, SSZ bit order: bgv_pkbits) */
+      bool by_index = false, by_committee = false;
+      napi_has_named_property(env, s, "committee", &by_committee);
       napi_has_named_property(env, s, "pkIndices", &by_index);
-      napi_get_named_property(env, s, by_index ? "pkIndices" : "pkBytes", &pk);
+      napi_get_named_property(env, s, by_committee ? "bits" : by_index ? "pkIndices" : "pkBytes", &pk);
       napi_get_named_property(env, s, "msg", &msg);
       napi_get_named_property(env, s, "sig", &sig);
+      bgv_pkbits* pb = &r->pkbits[r->nsets];
+      pb->committee = BGV_NO_COMMITTEE;
+      pb->n_bits = 0;
+      pb->bits = NULL;
       bgv_set* st = &r->sets[r->nsets++];
       memset(st, 0, sizeof(*st));
       uint8_t *pkd, *md, *sd;
       size_t pkl, ml, sl;
       if (get_bytes(env, pk, &pkd, &pkl) || get_bytes(env, msg, &md, &ml) || get_bytes(env, sig, &sd, &sl) ||
-          ml != 32 || (!by_index && pkl % 96)) {
+          ml != 32 || (!by_index && !by_committee && pkl % 96)) {
         free_req(env, r);
         return throw_code(env, -BGV_E_ARG);
       }
-      if (by_index) {
+      if (by_committee) {
+        napi_value cv, nv;
+        uint32_t cid = 0, nbits = 0;
+        napi_get_named_property(env, s, "committee", &cv);
+        napi_get_named_property(env, s, "nBits", &nv);
+        if (napi_get_value_uint32(env, cv, &cid) != napi_ok || napi_get_value_uint32(env, nv, &nbits) != napi_ok ||
+            cid == BGV_NO_COMMITTEE || pkl != ((size_t)nbits + 7) / 8) {
+          free_req(env, r);
+          return throw_code(env, -BGV_E_ARG);
+        }
+        pb->committee = cid;
+        pb->n_bits = nbits;
+        pb->bits = pkd;
+        r->any_committee = 1;
+      } else if (by_index) {
         st->n_pk = (uint32_t)(pkl / 4);
         st->pk_indices = (const uint32_t*)pkd;
       } else {
@@ -665,7 +743,8 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   /* the ctx external stays alive (no finalizer) until this request completes */
   CHECK(env, napi_create_reference(env, argv[0], 1, &r->ctx_ref));
   if (a->inflight++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
-  int rc = bgv_verify_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->mode, r->codes, &r->stats, verify_done, r);
+  int rc = bgv_verify_bits_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_committee ? r->pkbits : NULL,
+                                 r->mode, r->codes, &r->stats, verify_done, r);
   if (rc) { /* rejected before queueing (closed, bad arguments): settle now */
     r->rc = rc;
     settle(env, r);
@@ -688,6 +767,9 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"sign", NULL, js_sign, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"verify", NULL, js_verify, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregatePubkeys", NULL, js_aggregate_pubkeys, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"committeePut", NULL, js_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"aggregateCommitteeBits", NULL, js_aggregate_committee_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"hashToG2", NULL, js_hash_to_g2, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"pubkeysValidate", NULL, js_pubkeys_validate, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregateSignatures", NULL, js_aggregate_signatures, NULL, NULL, NULL, METHOD_ATTR, NULL},

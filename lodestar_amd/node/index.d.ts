@@ -18,7 +18,11 @@ export interface IBlsVerifier {
   close(): Promise<void>;
 }
 
-export declare const SignatureSetType: {readonly single: "single"; readonly aggregate: "aggregate"};
+export declare const SignatureSetType: {
+  readonly single: "single";
+  readonly aggregate: "aggregate";
+  readonly committee: "committee";
+};
 export type SignatureSetType = typeof SignatureSetType[keyof typeof SignatureSetType];
 
 /** a cached validator index, a PublicKey tagged with its index, or uncompressed key bytes */
@@ -36,7 +40,21 @@ export interface IAggregatedSignatureSet {
   signingRoot: Uint8Array;
   signature: Uint8Array;
 }
-export type ISignatureSet = ISingleSignatureSet | IAggregatedSignatureSet;
+/**
+ * Not in the reference: the aggregate as the node holds it before bits.intersectValues -- a
+ * committee stored with BlsGpuVerifier.committeePut and the participation bitfield (member k
+ * takes part iff (bits[k >> 3] >> (k & 7)) & 1).  bits: ceil(nBits / 8) bytes with nBits beside
+ * it, or a BitArray.
+ */
+export interface ICommitteeSignatureSet {
+  type: "committee";
+  committee: number;
+  bits: Uint8Array | {uint8Array: Uint8Array; bitLen: number};
+  nBits?: number;
+  signingRoot: Uint8Array;
+  signature: Uint8Array;
+}
+export type ISignatureSet = ISingleSignatureSet | IAggregatedSignatureSet | ICommitteeSignatureSet;
 
 export interface BlsGpuVerifierOpts {
   devices?: number[];
@@ -63,6 +81,10 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   pubkeyAddedHook(): (index: number, pubkey: Uint8Array, pk?: object) => void;
   /** uploads the queued keys off the event loop; verifySignatureSets awaits it */
   flushPubkeys(): Promise<void>;
+  /** stores a committee (validator indices, their pubkey sum) on the device(s) under id 0..16383 */
+  committeePut(id: number, indices: Uint32Array | number[]): Promise<void>;
+  /** frees the id at once; queued calls finish on the committee they named */
+  committeeDrop(id: number): void;
   onPubkeyError: ((e: Error, first: number, n: number) => void) | null;
   isValidBlsAggregate(publicKeys: PubkeyRef[], message: Uint8Array, signature: Uint8Array): Promise<boolean>;
   aggregateSignatures(sigs: Uint8Array[]): Uint8Array;

@@ -42,7 +42,7 @@ const G2_POINT_AT_INFINITY = (() => {
   b[0] = 0xc0;
   return b;
 })();
-const SignatureSetType = {single: "single", aggregate: "aggregate"};
+const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee"};
 
 const ssz = require("./ssz.js");
 
@@ -200,6 +200,34 @@ function getAttestationWithIndicesSignatureSet(state, attestation, indices, type
   };
 }
 
+/** A BitArray ({uint8Array, bitLen}) or plain bytes -> {bits, nBits} of a committee set */
+function bitsOf(bits, nBits) {
+  const bytes = bits.uint8Array || bits;
+  const n = bits.bitLen !== undefined ? bits.bitLen : nBits;
+  return {bits: Uint8Array.from(bytes.subarray(0, (n + 7) >> 3)), nBits: n};
+}
+
+/**
+ * The attestation's set without the expansion of epochContext.ts:620-622
+ * (bits.intersectValues(committeeIndices)): the beacon committee is on the device under
+ * committeeId (BlsGpuVerifier.committeePut) and the set carries attestation.aggregationBits.
+ * Same domain and signing root as getAttestationWithIndicesSignatureSet.
+ */
+function getAttestationBitsSignatureSet(state, attestation, committeeId, types) {
+  const slot = computeStartSlotAtEpoch(attestation.data.target.epoch);
+  const domain = state.config.getDomain(state.slot, DOMAIN_BEACON_ATTESTER, slot);
+  const committee = state.epochCtx.getBeaconCommittee
+    ? state.epochCtx.getBeaconCommittee(attestation.data.slot, attestation.data.index)
+    : null;
+  return {
+    type: SignatureSetType.committee,
+    committee: committeeId,
+    ...bitsOf(attestation.aggregationBits, committee ? committee.length : undefined),
+    signingRoot: computeSigningRoot(rootOf(types, "AttestationData", attestation.data), domain),
+    signature: attestation.signature,
+  };
+}
+
 /** indexedAttestation.ts:23-28 */
 function getIndexedAttestationSignatureSet(state, indexedAttestation, types) {
   return getAttestationWithIndicesSignatureSet(state, indexedAttestation, indexedAttestation.attestingIndices, types);
@@ -267,6 +295,29 @@ function getSyncCommitteeSignatureSet(state, block, participantIndices, types) {
   };
 }
 
+/** getSyncCommitteeSignatureSet without intersectBits: the current sync committee is on the
+ * device under committeeId and the set carries syncAggregate.syncCommitteeBits.  null when
+ * nobody participated (and the signature is the point at infinity). */
+function getSyncCommitteeBitsSignatureSet(state, block, committeeId, types) {
+  const {syncAggregate} = block.body;
+  const signature = syncAggregate.syncCommitteeSignature;
+  const previousSlot = Math.max(block.slot, 1) - 1;
+  const size = state.epochCtx.currentSyncCommitteeIndexed.validatorIndices.length;
+  const b = bitsOf(syncAggregate.syncCommitteeBits, size);
+  if (b.bits.every((v) => v === 0)) {
+    if (bytesEqual(signature, G2_POINT_AT_INFINITY)) return null;
+    throw Error("Empty sync committee signature is not infinity");
+  }
+  const domain = state.config.getDomain(state.slot, DOMAIN_SYNC_COMMITTEE, previousSlot);
+  return {
+    type: SignatureSetType.committee,
+    committee: committeeId,
+    ...b,
+    signingRoot: computeSigningRoot(rootOf(types, "Root", block.parentRoot), domain),
+    signature,
+  };
+}
+
 /** index.ts:23-56: randao, proposer slashings, attester slashings, attestations, exits,
  * [proposer], [sync aggregate] — deposits excluded (they may carry invalid signatures) */
 function getBlockSignatureSets(state, signedBlock, opts, types) {
@@ -316,4 +367,6 @@ module.exports = {
   getVoluntaryExitSignatureSet,
   getVoluntaryExitsSignatureSets,
   getSyncCommitteeSignatureSet,
+  getAttestationBitsSignatureSet,
+  getSyncCommitteeBitsSignatureSet,
 };

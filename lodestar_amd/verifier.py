@@ -37,6 +37,10 @@ class SignatureSetType(enum.Enum):
     """state-transition/src/util/signatureSets.ts:5-8"""
     single = "single"
     aggregate = "aggregate"
+    # not in the reference: the aggregate as the beacon node holds it before
+    # bits.intersectValues(committeeIndices) (epochContext.ts:620-622) -- a committee kept on
+    # the device (native.Context.committee_put) and the participation bitfield
+    committee = "committee"
 
 
 # A public key is a validator index into the device cache (int) or 96 uncompressed bytes.
@@ -51,6 +55,11 @@ class ISignatureSet:
     signature: bytes
     pubkey: Optional[PublicKey] = None
     pubkeys: List[PublicKey] = field(default_factory=list)
+    # type == committee: the committee's id, the SSZ bitfield (member k takes part iff
+    # (bits[k >> 3] >> (k & 7)) & 1) and its length in bits (the committee's size)
+    committee: Optional[int] = None
+    bits: Optional[bytes] = None
+    n_bits: Optional[int] = None
 
 
 @dataclass
@@ -77,13 +86,16 @@ def chunkify_maximize_chunk_size(arr: Sequence, min_per_chunk: int) -> List[list
 
 
 def get_aggregated_pubkeys_count(sets: Sequence[ISignatureSet]) -> int:
-    """utils.ts:18-26"""
-    return sum(len(s.pubkeys) for s in sets if s.type == SignatureSetType.aggregate)
+    """utils.ts:18-26; a committee set counts the members whose bit is set"""
+    return sum(len(s.pubkeys) for s in sets if s.type == SignatureSetType.aggregate) + \
+        sum(bin(b).count("1") for s in sets if s.type == SignatureSetType.committee for b in s.bits)
 
 
 def to_set_spec(s: ISignatureSet) -> native.SetSpec:
     """getAggregatedPubkey + serialisation (utils.ts:5-16, index.ts:158-163): the
     aggregation itself happens on the device."""
+    if s.type == SignatureSetType.committee:
+        return native.SetSpec(s.signing_root, s.signature, committee=s.committee, bits=s.bits, n_bits=s.n_bits)
     if s.type == SignatureSetType.single:
         pks = [s.pubkey]
     elif s.type == SignatureSetType.aggregate:
