@@ -163,6 +163,34 @@ int bgv_verify_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_
 int bgv_committee_put(bgv_ctx* ctx, uint32_t id, const uint32_t* indices, size_t n);
 int bgv_committee_drop(bgv_ctx* ctx, uint32_t id);
 
+/* All committees of one epoch in one call: the device computes the epoch's shuffling and cuts it
+ * into count = slots * committees_per_slot committees, ids first_id .. first_id + count - 1.
+ * Replaces computeEpochShuffling with unshuffleList (state-transition/src/util/epochShuffling.ts:59-97,
+ * util/shuffle.ts) and the bgv_committee_put per committee that would follow it:
+ *   shuffling[i] = active_indices[p(i)], p(i) the spec's compute_shuffled_index(i, n_active, seed)
+ *   over `rounds` swap-or-not rounds r = 0 .. rounds - 1 (pivot = LE64(sha256(seed | r)[0:8]) mod n,
+ *   flip = (pivot + n - i) mod n, pos = max(i, flip), src = sha256(seed | r | LE32(pos >> 8)),
+ *   i = flip iff (src[(pos & 255) >> 3] >> (pos & 7)) & 1);
+ *   committee k = slot * committees_per_slot + index is
+ *   shuffling[floor(n k / count), floor(n (k + 1) / count)).
+ * The host passes the preset: slots (SLOTS_PER_EPOCH), committees_per_slot (computeCommitteeCount)
+ * and rounds (SHUFFLE_ROUND_COUNT; at most 255); rounds == 0 or n_active == 1 leave the list as it
+ * is.  out_shuffling (may be NULL) receives the n_active shuffled indices, IEpochShuffling.shuffling.
+ * A non-empty committee is a committee in every respect (sets, bgv_aggregate_committee_bits,
+ * bgv_committee_drop, recomputed after a bgv_pubkeys_put over a member); an empty one
+ * (n_active < count) gets no id.  All or nothing: on an error no id of the range exists.
+ * -BGV_E_ARG: n_active < 1 or > 2^22, slots or committees_per_slot 0, first_id + count >
+ * BGV_MAX_COMMITTEES, rounds > 255, a committee longer than 65536, an id of the range still live;
+ * -BGV_E_BAD_INDEX: an index at or past bgv_pubkeys_count, or a marked one; -BGV_E_NOMEM: fewer
+ * free handles than non-empty committees.  Like bgv_committee_put it waits for running verifies
+ * only when the index pool has to grow.
+ * bgv_committee_drop_range drops the live ids of [first_id, first_id + count) and returns how
+ * many there were (>= 0); storage is reused as after bgv_committee_drop. */
+int bgv_shuffling_put(bgv_ctx* ctx, uint32_t first_id, const uint8_t seed[32], const uint32_t* active_indices,
+                      size_t n_active, uint32_t slots, uint32_t committees_per_slot, uint32_t rounds,
+                      uint32_t* out_shuffling);
+int bgv_committee_drop_range(bgv_ctx* ctx, uint32_t first_id, uint32_t count);
+
 /* The pubkeys of one set as committee members: member k takes part iff
  * (bits[k >> 3] >> (k & 7)) & 1 (SSZ bit order); bits holds ceil(n_bits / 8) bytes.
  * committee == BGV_NO_COMMITTEE: the set's own pk_indices / pk_bytes count. */

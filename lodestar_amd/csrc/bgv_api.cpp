@@ -43,6 +43,7 @@
 #include "bgv_launch.h"
 #include "bgv_retry_plan.h"  // with bgv_host_layout.h: the host-only layout and retry planning
 #include "bls_field.h"  // fp12_t (sizes of the per-group u copies)
+#include "bgv_shuffle.h"  // the committee bounds of an epoch shuffling (bgv_shuffling_put)
 
 // slots merged into one device super-batch (BGV_MAX_BATCH_SLOTS env)
 #define BGV_MAX_BATCH_SLOTS 131072
@@ -207,6 +208,22 @@ struct ComPool {
       }
     return false;
   }
+  // one range of n words and nh handles (an epoch's committees, bgv_shuffling_put: each of its
+  // records returns its own part of the range, which add_range joins again)
+  bool alloc_bulk(uint32_t n, uint32_t nh, std::vector<uint32_t>* handles, uint32_t* off) {  // under mu
+    if (free_handles.size() < nh) return false;
+    for (auto it = free_ranges.begin(); it != free_ranges.end(); ++it)
+      if (it->second >= n) {
+        *off = it->first;
+        const uint32_t rest = it->second - n;
+        free_ranges.erase(it);
+        if (rest) free_ranges.emplace(*off + n, rest);
+        handles->assign(free_handles.end() - nh, free_handles.end());
+        free_handles.resize(free_handles.size() - nh);
+        return true;
+      }
+    return false;
+  }
   void add_range(uint32_t off, uint32_t n) {  // under mu
     auto nx = free_ranges.lower_bound(off);
     if (nx != free_ranges.begin()) {
@@ -282,6 +299,8 @@ struct Device {
   bgv_dcommittee* com_dir = nullptr;  // kComHandles entries
   uint32_t* com_pool = nullptr;       // member indices of every committee (ComPool::cap words)
   uint32_t* com_list = nullptr;       // kComHandles words: the handles of one k_committee_total launch
+  uint32_t* shuf_buf = nullptr;       // bgv_shuffling_put's scratch (active indices, digest table, pivots)
+  size_t shuf_cap = 0;                // in words; grown on demand, under util_mu
   std::vector<Exec*> execs;
   // held while one super-batch runs its per-set kernels (pointer: Device stays movable)
   std::unique_ptr<std::mutex> compute_mu = std::make_unique<std::mutex>();
@@ -1180,9 +1199,11 @@ static void ctx_free_devices(bgv_ctx* c) {
     if (d.cache) (void)hipFree(d.cache);
     d.cache = nullptr;
     {
-      void* cbufs[] = {d.com_dir, d.com_pool, d.com_list};
+      void* cbufs[] = {d.com_dir, d.com_pool, d.com_list, d.shuf_buf};
       for (void* q : cbufs)
         if (q) (void)hipFree(q);
+      d.shuf_buf = nullptr;
+      d.shuf_cap = 0;
       d.com_dir = nullptr;
       d.com_pool = nullptr;
       d.com_list = nullptr;
@@ -1471,6 +1492,124 @@ int bgv_committee_drop(bgv_ctx* c, uint32_t id) {
                    c->retired.end());
   c->retired.push_back(rec);
   return BGV_OK;
+}
+
+// An epoch's committees in one call: the device shuffles the active indices straight into one
+// range of the index pool (k_shuffle_table, k_shuffle_walk), writes the directory entries of the
+// non-empty committees (k_shuffle_dir) and sums them (k_committee_total) -- one launch chain and
+// one synchronize per device.  The host mirror of every committee is cut from the shuffling read
+// back from the first device.  Locks as bgv_committee_put's.  Nothing is published before
+// everything succeeded, and the records give their handles and ranges back otherwise.
+int bgv_shuffling_put(bgv_ctx* c, uint32_t first_id, const uint8_t seed[32], const uint32_t* active, size_t n_active,
+                      uint32_t slots, uint32_t committees_per_slot, uint32_t rounds, uint32_t* out_shuffling) {
+  if (!c || !seed || !active || n_active < 1 || n_active > BGV_SHUFFLE_MAX_N || !slots || !committees_per_slot ||
+      rounds > BGV_SHUFFLE_MAX_ROUNDS)
+    return -BGV_E_ARG;
+  const uint64_t count64 = (uint64_t)slots * committees_per_slot;
+  if (first_id > BGV_MAX_COMMITTEES || count64 > BGV_MAX_COMMITTEES - first_id) return -BGV_E_ARG;
+  const uint32_t n = (uint32_t)n_active, count = (uint32_t)count64, m = shuf_nonempty(n, count);
+  if (shuf_longest(n, count) > 65536) return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  std::vector<std::shared_ptr<CommitteeRec>> recs;  // the non-empty committees, in order
+  std::vector<uint32_t> ks, handles;                // their numbers in the epoch, their handles
+  uint32_t base = 0;
+  auto checks = [&]() -> int {
+    if (c->closed) return -BGV_E_CLOSED;
+    {
+      std::shared_lock<std::shared_mutex> lk(c->com_mu);
+      for (uint32_t k = 0; k < count; ++k)
+        if (c->committees.count(first_id + k)) return -BGV_E_ARG;
+    }
+    const size_t npk = c->n_pubkeys;
+    const bool marks = !c->bad_pk.empty();
+    for (size_t i = 0; i < n; ++i)
+      if (active[i] >= npk || (marks && c->bad_pk.count(active[i]))) return -BGV_E_BAD_INDEX;
+    return BGV_OK;
+  };
+  auto take = [&]() -> bool {
+    std::lock_guard<std::mutex> lk(c->com_pool->mu);
+    if (!c->com_pool->alloc_bulk(n, m, &handles, &base)) return false;
+    for (uint32_t j = 0; j < m; ++j) {  // from here on the records give everything back
+      uint32_t lo, hi;
+      ks.push_back(shuf_nonempty_k(n, count, j, &lo, &hi));
+      auto rec = std::make_shared<CommitteeRec>();
+      rec->handle = handles[j];
+      rec->off = base + lo;
+      rec->idx.resize(hi - lo);
+      rec->pool = c->com_pool;
+      recs.push_back(std::move(rec));
+    }
+    return true;
+  };
+  auto run = [&]() -> int {
+    std::vector<uint32_t> shuf(n);
+    {
+      std::lock_guard<std::mutex> ulk(c->util_mu);
+      const size_t words = bgv_shuffle_scratch_words(n, rounds);
+      bool first = true;
+      for (Device& d : c->devs) {
+        HIPCHK(hipSetDevice(d.id));
+        if (d.shuf_cap < words) {
+          uint32_t* p = nullptr;
+          HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), 4 * words));
+          if (d.shuf_buf) (void)hipFree(d.shuf_buf);
+          d.shuf_buf = p;
+          d.shuf_cap = words;
+        }
+        HIPCHK(hipMemcpyAsync(d.shuf_buf, active, 4 * (size_t)n, hipMemcpyHostToDevice, d.stream));
+        HIPCHK(hipMemcpyAsync(d.com_list, handles.data(), 4 * (size_t)m, hipMemcpyHostToDevice, d.stream));
+        HIPCHK(bgv_launch_shuffle(seed, n, rounds, d.shuf_buf, d.com_pool + base, d.stream));
+        HIPCHK(bgv_launch_shuffle_dir(d.com_dir, d.com_list, m, base, n, count, d.stream));
+        HIPCHK(bgv_launch_committee_totals(d.com_dir, d.com_list, m, d.com_pool, d.cache, d.stream));
+        if (first)
+          HIPCHK(hipMemcpyAsync(shuf.data(), d.com_pool + base, 4 * (size_t)n, hipMemcpyDeviceToHost, d.stream));
+        first = false;
+        HIPCHK(hipStreamSynchronize(d.stream));
+      }
+    }
+    for (uint32_t j = 0; j < m; ++j) {
+      CommitteeRec& r = *recs[j];
+      std::copy_n(shuf.begin() + (r.off - base), r.idx.size(), r.idx.begin());
+    }
+    if (out_shuffling) memcpy(out_shuffling, shuf.data(), 4 * (size_t)n);
+    std::unique_lock<std::shared_mutex> lk(c->com_mu);
+    for (uint32_t j = 0; j < m; ++j) c->committees.emplace(first_id + ks[j], recs[j]);
+    return BGV_OK;
+  };
+  {
+    std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+    if (int rc = checks()) return rc;
+    if (take()) return run();
+    std::lock_guard<std::mutex> lk(c->com_pool->mu);
+    if (c->com_pool->free_handles.size() < m) return -BGV_E_NOMEM;  // the rest are live or still referenced
+  }
+  std::unique_lock<std::shared_mutex> clk(c->cache_mu);
+  if (int rc = checks()) return rc;
+  {
+    std::lock_guard<std::mutex> ulk(c->util_mu);
+    if (int rc = com_pool_grow(c, n)) return rc;
+  }
+  if (!take()) return -BGV_E_NOMEM;
+  return run();
+}
+
+int bgv_committee_drop_range(bgv_ctx* c, uint32_t first_id, uint32_t count) {
+  if (!c || first_id > BGV_MAX_COMMITTEES || count > BGV_MAX_COMMITTEES - first_id) return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  if (c->closed) return -BGV_E_CLOSED;
+  std::vector<std::shared_ptr<CommitteeRec>> recs;  // released after com_mu, as in bgv_committee_drop
+  std::unique_lock<std::shared_mutex> lk(c->com_mu);
+  c->retired.erase(std::remove_if(c->retired.begin(), c->retired.end(),
+                                  [](const std::weak_ptr<CommitteeRec>& w) { return w.expired(); }),
+                   c->retired.end());
+  for (uint32_t id = first_id; id < first_id + count; ++id) {
+    auto it = c->committees.find(id);
+    if (it == c->committees.end()) continue;
+    c->retired.push_back(it->second);
+    recs.push_back(std::move(it->second));
+    c->committees.erase(it);
+  }
+  return (int)recs.size();
 }
 
 // Decode n records into per-device staging buffers (the slow part: host-to-device copy and

@@ -122,6 +122,16 @@ hipError_t bgv_launch_aggregate_bits(const bgv_dslot* slot, const uint32_t* idx,
 // the pubkey sums of the committees in handles into their directory entries
 hipError_t bgv_launch_committee_totals(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, const uint32_t* pool,
                                        const bgv_cache_entry* cache, hipStream_t st);
+// Epoch shuffling (bgv_k_shuffle.hip).  scratch holds bgv_shuffle_scratch_words words, the n
+// active indices in its first n; out[i] = active[compute_shuffled_index(i, n, seed)] over
+// rounds rounds (k_shuffle_table + k_shuffle_walk).  bgv_launch_shuffle_dir writes {off, n} of
+// the shuffling's nh non-empty committees (of count, members at pool[base ..)) into the
+// directory entries handles[0 .. nh).
+size_t bgv_shuffle_scratch_words(uint32_t n, uint32_t rounds);
+hipError_t bgv_launch_shuffle(const uint8_t seed[32], uint32_t n, uint32_t rounds, uint32_t* scratch, uint32_t* out,
+                              hipStream_t st);
+hipError_t bgv_launch_shuffle_dir(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, uint32_t base, uint32_t n,
+                                  uint32_t count, hipStream_t st);
 size_t bgv_g1_point_bytes();
 hipError_t bgv_launch_debug_out(const bgv_dev_batch& b, uint8_t* out_h192, uint8_t* out_f576, hipStream_t st);
 hipError_t bgv_launch_hash(const uint8_t* msgs, const uint32_t* offs, const uint32_t* lens, uint32_t n,

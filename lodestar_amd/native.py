@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "bgv_pubkeys_validate", "bgv_aggregate_signatures", "bgv_deposits_verify", "bgv_set_batching",
     "bgv_verify_partial", "bgv_final_verify", "bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split",
     "bgv_committee_put", "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
-    "bgv_aggregate_committee_bits",
+    "bgv_aggregate_committee_bits", "bgv_shuffling_put", "bgv_committee_drop_range",
 ]
 
 
@@ -127,11 +127,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_verify_bits": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P], ctypes.c_int),
             "bgv_verify_bits_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, DONE_FN, P], ctypes.c_int),
             "bgv_aggregate_committee_bits": ([P, U32, P, U32, P], ctypes.c_int),
+            "bgv_shuffling_put": ([P, U32, P, P, SZ, U32, U32, U32, P], ctypes.c_int),
+            "bgv_committee_drop_range": ([P, U32, U32], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
                         "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
-                        "bgv_aggregate_committee_bits") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_aggregate_committee_bits", "bgv_shuffling_put",
+                        "bgv_committee_drop_range") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -248,6 +251,24 @@ class Context:
 
     def committee_drop(self, committee_id: int):
         _check(self.lib.bgv_committee_drop(self._h, committee_id))
+
+    def shuffling_put(self, first_id: int, seed: bytes, active_indices: Sequence[int], slots: int,
+                      committees_per_slot: int, rounds: int = 90):
+        """An epoch's committees in one call (bgv_shuffling_put): the device shuffles active_indices
+        (swap-or-not over `rounds` rounds, computeEpochShuffling with unshuffleList), stores the
+        slots * committees_per_slot committees under first_id, first_id + 1, ... (an empty one gets
+        no id) and sums their pubkeys.  Returns the shuffled indices (numpy uint32 array)."""
+        import numpy as np
+        assert len(seed) == 32
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        out = np.empty(max(1, act.size), dtype=np.uint32)
+        _check(self.lib.bgv_shuffling_put(self._h, first_id, _buf(bytes(seed)), act.ctypes.data, act.size, slots,
+                                          committees_per_slot, rounds, out.ctypes.data))
+        return out[:act.size]
+
+    def committee_drop_range(self, first_id: int, count: int) -> int:
+        """Drop the live committees of ids first_id .. first_id + count - 1; returns how many."""
+        return _check(self.lib.bgv_committee_drop_range(self._h, first_id, count))
 
     def aggregate_committee_bits(self, committee_id: int, bits: bytes, n_bits: int) -> bytes:
         """The aggregate of the committee members whose bit is set (SSZ bit order), 96 B

@@ -275,6 +275,24 @@ class BlsGpuVerifier {
     addon.committeeDrop(this.ctx, id);
   }
 
+  /**
+   * All committees of one epoch in one call (INTEGRATION.md §2c): the device shuffles
+   * `activeIndices` with `seed` (computeEpochShuffling with unshuffleList, over `rounds`
+   * swap-or-not rounds), stores the slots * committeesPerSlot committees under firstId,
+   * firstId + 1, ... and sums their pubkeys.  Runs off the event loop; resolves to the epoch's
+   * shuffling (IEpochShuffling.shuffling).  The queued pubkeys go first.
+   */
+  async shufflingPut(firstId, seed, activeIndices, slots, committeesPerSlot, rounds) {
+    await this.flushPubkeys();
+    const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+    return addon.shufflingPut(this.ctx, firstId, seed, active, slots, committeesPerSlot, rounds);
+  }
+
+  /** Drops the live ids of firstId .. firstId + count - 1 (an epoch's committees); returns how many. */
+  committeeDropRange(firstId, count) {
+    return addon.committeeDropRange(this.ctx, firstId, count);
+  }
+
   // index.ts:176-197.  Idempotent; device calls already in flight complete (the library
   // drains them before releasing the context), queued and later jobs reject QUEUE_ABORTED.
   async close() {

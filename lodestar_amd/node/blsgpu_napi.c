@@ -385,6 +385,107 @@ static napi_value js_committee_drop(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* committeeDropRange(ctx, firstId, count) -> number: bgv_committee_drop_range, the live ids of the
+ * range dropped (host-only work). */
+static napi_value js_committee_drop_range(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t first = 0, count = 0;
+  if (argc < 3 || napi_get_value_uint32(env, argv[1], &first) != napi_ok ||
+      napi_get_value_uint32(env, argv[2], &count) != napi_ok)
+    return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_committee_drop_range(ctx, first, count);
+  if (rc < 0) return throw_code(env, rc);
+  CHECK(env, napi_create_int32(env, rc, &out));
+  return out;
+}
+
+/* shufflingPut(ctx, firstId, seed: Uint8Array(32), activeIndices: Uint32Array, slots,
+ * committeesPerSlot, rounds) -> Promise<Uint32Array>: bgv_shuffling_put on a libuv pool thread (the
+ * device call never holds the event loop); resolves to the epoch's shuffling
+ * (IEpochShuffling.shuffling, util/epochShuffling.ts:90-96), rejects with an Error whose .bgvCode
+ * is the negative library code. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  napi_ref ctx_ref, act_ref, out_ref;
+  bgv_ctx* c;
+  uint32_t first, slots, cps, rounds;
+  uint8_t seed[32];
+  const uint32_t* active;
+  uint32_t* out;
+  size_t n;
+  int rc;
+} shuf_req;
+
+static void shuf_execute(napi_env env, void* data) {
+  (void)env;
+  shuf_req* r = (shuf_req*)data;
+  r->rc = bgv_shuffling_put(r->c, r->first, r->seed, r->active, r->n, r->slots, r->cps, r->rounds, r->out);
+}
+
+static void shuf_complete(napi_env env, napi_status status, void* data) {
+  shuf_req* r = (shuf_req*)data;
+  napi_value out;
+  if (status == napi_ok && r->rc == 0 && napi_get_reference_value(env, r->out_ref, &out) == napi_ok) {
+    napi_resolve_deferred(env, r->deferred, out);
+  } else {
+    const int rc = status == napi_ok && r->rc ? r->rc : -BGV_E_ARG;
+    napi_value msg, err, code;
+    napi_create_string_utf8(env, bgv_strerror(rc), NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int32(env, rc, &code);
+    napi_set_named_property(env, err, "bgvCode", code);
+    napi_reject_deferred(env, r->deferred, err);
+  }
+  napi_delete_reference(env, r->ctx_ref);
+  napi_delete_reference(env, r->act_ref);
+  napi_delete_reference(env, r->out_ref);
+  napi_delete_async_work(env, r->work);
+  free(r);
+}
+
+static napi_value js_shuffling_put(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7], promise, name, ab, out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint8_t *seed, *act;
+  size_t seed_len, act_len;
+  uint32_t first = 0, slots = 0, cps = 0, rounds = 0;
+  if (argc < 7 || napi_get_value_uint32(env, argv[1], &first) != napi_ok ||
+      get_bytes(env, argv[2], &seed, &seed_len) || seed_len != 32 || get_bytes(env, argv[3], &act, &act_len) ||
+      act_len % 4 || act_len == 0 || napi_get_value_uint32(env, argv[4], &slots) != napi_ok ||
+      napi_get_value_uint32(env, argv[5], &cps) != napi_ok || napi_get_value_uint32(env, argv[6], &rounds) != napi_ok)
+    return throw_code(env, -BGV_E_ARG);
+  void* dst;
+  CHECK(env, napi_create_arraybuffer(env, act_len, &dst, &ab));
+  CHECK(env, napi_create_typedarray(env, napi_uint32_array, act_len / 4, ab, 0, &out));
+  shuf_req* r = (shuf_req*)calloc(1, sizeof(shuf_req));
+  r->c = ctx;
+  r->first = first;
+  r->slots = slots;
+  r->cps = cps;
+  r->rounds = rounds;
+  memcpy(r->seed, seed, 32);
+  r->active = (const uint32_t*)act;
+  r->out = (uint32_t*)dst;
+  r->n = act_len / 4;
+  if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
+      napi_create_reference(env, argv[0], 1, &r->ctx_ref) != napi_ok ||
+      napi_create_reference(env, argv[3], 1, &r->act_ref) != napi_ok ||
+      napi_create_reference(env, out, 1, &r->out_ref) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu.shufflingPut", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, shuf_execute, shuf_complete, r, &r->work) != napi_ok ||
+      napi_queue_async_work(env, r->work) != napi_ok) {
+    napi_throw_error(env, NULL, "blsgpu: N-API failure");
+    return NULL;
+  }
+  return promise;
+}
+
 /* aggregateCommitteeBits(ctx, id, bits: Uint8Array, nBits) -> Uint8Array(96): the aggregate of the
  * committee members whose bit is set, through the verify path's kernel (parity hook). */
 static napi_value js_aggregate_committee_bits(napi_env env, napi_callback_info info) {
@@ -769,6 +870,8 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"aggregatePubkeys", NULL, js_aggregate_pubkeys, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeePut", NULL, js_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"committeeDropRange", NULL, js_committee_drop_range, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"shufflingPut", NULL, js_shuffling_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregateCommitteeBits", NULL, js_aggregate_committee_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"hashToG2", NULL, js_hash_to_g2, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"pubkeysValidate", NULL, js_pubkeys_validate, NULL, NULL, NULL, METHOD_ATTR, NULL},

@@ -85,6 +85,21 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   committeePut(id: number, indices: Uint32Array | number[]): Promise<void>;
   /** frees the id at once; queued calls finish on the committee they named */
   committeeDrop(id: number): void;
+  /**
+   * an epoch's committees in one device call: shuffles activeIndices with seed over `rounds`
+   * swap-or-not rounds, stores the slots * committeesPerSlot committees under firstId, firstId + 1, ...
+   * and resolves to the shuffling (IEpochShuffling.shuffling)
+   */
+  shufflingPut(
+    firstId: number,
+    seed: Uint8Array,
+    activeIndices: Uint32Array,
+    slots: number,
+    committeesPerSlot: number,
+    rounds: number
+  ): Promise<Uint32Array>;
+  /** drops the live ids of firstId .. firstId + count - 1; returns how many there were */
+  committeeDropRange(firstId: number, count: number): number;
   onPubkeyError: ((e: Error, first: number, n: number) => void) | null;
   isValidBlsAggregate(publicKeys: PubkeyRef[], message: Uint8Array, signature: Uint8Array): Promise<boolean>;
   aggregateSignatures(sigs: Uint8Array[]): Uint8Array;
