@@ -13,24 +13,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libblsgpu.so")
 # kernel translation units (compiled in parallel; each carries its own copy of the
-# out-of-line arithmetic with its own register budget) and the host orchestration
+# out-of-line arithmetic with its own register budget) and the host orchestration units
 KERNEL_UNITS = ["bgv_k_prep_bulk.hip", "bgv_k_miller_bulk.hip", "bgv_k_prep.hip", "bgv_k_prep_wave.hip", "bgv_k_miller.hip", "bgv_k_final.hip", "bgv_k_util.hip", "bgv_k_shuffle.hip"]
-SOURCES = [os.path.join(CSRC, f) for f in KERNEL_UNITS] + [os.path.join(CSRC, "bgv_api.cpp")]
+HOST_UNITS = ["bgv_sched.cpp", "bgv_registry.cpp", "bgv_calls.cpp"]
+SOURCES = [os.path.join(CSRC, f) for f in KERNEL_UNITS + HOST_UNITS]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("BGV_OFFLOAD_ARCH", "gfx950")
-
-
-def deps():
-    out = list(SOURCES) + [os.path.join(HERE, "..", "include", "blsgpu.h")]
-    out += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    return out
-
-
-def up_to_date(lib=LIB):
-    return os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in deps())
-
-
-OBJ_DIR = os.path.join(HERE, "..", "build", "obj")
 
 
 def _headers():
@@ -38,10 +26,17 @@ def _headers():
     return out + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
 
 
+def up_to_date(lib=LIB):
+    return os.path.exists(lib) and all(os.path.getmtime(lib) >= os.path.getmtime(d) for d in SOURCES + _headers())
+
+
+OBJ_DIR = os.path.join(HERE, "..", "build", "obj")
+
+
 def build(force=False, verbose=True, lib=LIB, defines=(), extra_flags=()):
     """defines: extra -D flags, extra_flags: extra compiler flags (A/B builds to another `lib`
     path: tools/ab_build.py; the product build takes neither).  Objects are
-    cached per source under build/obj (the kernel unit takes minutes; the host unit seconds)
+    cached per source under build/obj (a kernel unit takes minutes; a host unit seconds)
     and rebuilt when the source or any header is newer."""
     if not force and up_to_date(lib):
         return lib

@@ -1,5 +1,5 @@
 // Host-only layout of one verify call: its jobs' sets -> slots and device groups (bgv_layout.h).
-// No HIP here: bgv_api.cpp includes it for the library, tests/native/retrysim.cpp for a CPU
+// No HIP here: bgv_ctx.h includes it for the library, tests/native/retrysim.cpp for a CPU
 // simulation of the layout and the retry planner (bgv_retry_plan.h).
 #pragma once
 #include <stdint.h>
@@ -142,7 +142,7 @@ struct Layout {
   std::vector<uint32_t> com_team, com_wave;
 };
 
-// A call's slot as it stands in a merged super-batch (bgv_api.cpp run_pass1): after slot_base
+// A call's slot as it stands in a merged super-batch (bgv_sched.cpp run_pass1): after slot_base
 // slots, ib words of the index array, pb 96-byte pubkey records and gb groups of earlier calls.
 // A committee slot's run (handle and bit words) lies in the index array like a run of indices.
 inline bgv_dslot rebase_slot(bgv_dslot s, uint32_t slot_base, uint32_t ib, uint32_t pb, uint32_t gb) {

@@ -479,7 +479,7 @@ hipError_t bgv_launch_sets(const bgv_dev_batch& b, const bgv_streams& s) {
 
 // retry rounds over parts of failed groups: the parts' signature sums and pairs; with uniform
 // groups (b.uniform) also the pubkey sums and pubkey-sum pairs of the tests flagged
-// BGV_GROUP_UNIFORM (their slots have no own pair: bgv_api.cpp call_build_parts)
+// BGV_GROUP_UNIFORM (their slots have no own pair: bgv_retry_plan.h build_parts)
 hipError_t bgv_launch_gpairs(const bgv_dev_batch& b, hipStream_t st) {
   if (b.ngroups == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gsum, dim3(nblk(b.ngroups, BGV_FINAL_TEAMS)), dim3(64), 0, st, b.groups, b.ngroups, b.slots,

@@ -1,5 +1,5 @@
 // Per-set preparation kernels (gfx950) other than the bulk k_prep (bgv_k_prep_bulk.hip);
-// see bgv_api.cpp for the launch order of a verify call and bgv_k_miller.hip /
+// see bgv_sched.cpp for the launch order of a verify call and bgv_k_miller.hip /
 // bgv_k_final.hip for the rest.
 //
 //   k_pk_agg16 / k_pk_agg  (only when a call holds a set with >= BGV_PK_TREE_MIN cached

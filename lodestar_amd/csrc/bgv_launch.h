@@ -1,5 +1,5 @@
 // Internal interface between the HIP kernels (bgv_kernels.hip) and the host
-// orchestration (bgv_api.cpp).  Device pointers only; no torch types.
+// orchestration (bgv_sched.cpp, bgv_registry.cpp, bgv_calls.cpp).  Device pointers only; no torch types.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

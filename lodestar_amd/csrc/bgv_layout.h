@@ -1,5 +1,5 @@
 // Device-side record layouts shared by the HIP kernels (bgv_kernels.hip) and
-// the host orchestration (bgv_api.cpp).  Plain C structs, no HIP types.
+// the host orchestration (bgv_sched.cpp, bgv_registry.cpp, bgv_calls.cpp).  Plain C structs, no HIP types.
 //
 // A verify call is laid out as SLOTS: one lane per signature set.  Sets are
 // packed into device GROUPS of at most 64 slots that never straddle a 64-slot

@@ -1,6 +1,6 @@
 // Host-only retry planning of one verify call: from the first pass's statuses and group
 // verdicts to per-job codes, through rounds of group tests over the per-set results already on
-// the device.  No HIP here: bgv_api.cpp uploads the bgv_dgroup records a round asks for and
+// the device.  No HIP here: bgv_sched.cpp uploads the bgv_dgroup records a round asks for and
 // hands back the verdict words; tests/native/retrysim.cpp does the same with a model of the
 // closing kernels.
 #pragma once

@@ -2,7 +2,7 @@
 // unshuffleList (state-transition/src/util/shuffle.ts) and the committee bounds of
 // computeEpochShuffling (util/epochShuffling.ts).  Plain host/device functions (no HIP types):
 // k_shuffle_table / k_shuffle_walk / k_shuffle_dir (bgv_k_shuffle.hip) run them per thread, the
-// host (bgv_api.cpp) cuts its mirror with the bounds and tests/native/shufflesim.cpp runs all of
+// host (bgv_registry.cpp) cuts its mirror with the bounds and tests/native/shufflesim.cpp runs all of
 // it on a CPU.
 //
 // Round r (one byte) of a list of n positions has a pivot LE64(sha256(seed | r)[0:8]) mod n and

@@ -20,7 +20,7 @@ Here a call spreads over GPUs, one process each, in two ways:
   the CPU), and every rank multiplies them and runs the single final exponentiation
   (bgv_final_verify), so all ranks return the same code without a second collective.
 
-Error precedence follows job_precheck (bgv_api.cpp) / maybeBatch.ts:16-39 over the whole
+Error precedence follows job_precheck (bgv_retry_plan.h) / maybeBatch.ts:16-39 over the whole
 job: the first undecodable signature in set order (rank order = set order), else the first
 pubkey condition (infinity aggregate: BLST_PK_IS_INFINITY for >= 2 sets, false for one set).
 A device error on any rank never becomes a verdict: every rank joins the collective with

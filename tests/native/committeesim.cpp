@@ -189,7 +189,7 @@ int run_layout() {
         if (!sin) die("bad set line");
         S.push_back(std::move(s));
       }
-      // the call as bgv_api.cpp's call_submit sees it
+      // the call as bgv_sched.cpp's call_submit sees it
       const size_t n = S.size();
       std::vector<bgv_set> sets(n);
       std::vector<bgv_pkbits> pkb(n);
@@ -226,7 +226,7 @@ int run_layout() {
       die("unknown line: " + op);
     }
   }
-  // the calls merged into one super-batch (bgv_api.cpp run_pass1)
+  // the calls merged into one super-batch (bgv_sched.cpp run_pass1)
   uint32_t ns = 0, ni = 0, npb = 0, ng = 0;
   std::vector<uint32_t> midx, team, wave;
   for (const auto& Lp : layouts) {

@@ -4,7 +4,7 @@ One call over several devices (bgv_set_split; advisor r04): a job big enough to 
 per-device runs takes its host-side checks (an index not in the cache, an empty aggregate) on
 the whole job before it is cut, so they decide the job ahead of any device status -- an
 undecodable signature in an earlier run included -- exactly as in the unsplit call
-(bgv_api.cpp job_precheck; the reference raises them before any crypto:
+(bgv_retry_plan.h job_precheck; the reference raises them before any crypto:
 packages/beacon-node/src/chain/bls/maybeBatch.ts:16-39, chain/bls/utils.ts:5-16).  A one-set job
 is never cut (bgv_set_split(1) acts as 2).
 """

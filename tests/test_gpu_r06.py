@@ -126,7 +126,7 @@ def test_rns_engine_probe():
 
 
 # ---------------------------------------------------------------------------------------
-# Root-aligned layout (round 6, bgv_api.cpp call_submit): roots with >= 32 one-set jobs start
+# Root-aligned layout (round 6, bgv_sched.cpp call_submit): roots with >= 32 one-set jobs start
 # device groups of their own, the smaller roots share mixed groups after them; a pattern unit
 # whose every index bit failed both ways goes to singles.  Roots of 100, 40, 33, 32, 31, 5 and 1
 # jobs interleaved in call order, wrong keys inside the large roots, a mixed region whose jobs

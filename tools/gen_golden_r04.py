@@ -44,7 +44,7 @@ def splitmix64(state):
 
 
 def randomizers(seed, n):
-    """bgv_api.cpp bgv_debug_prepare: the i-th nonzero splitmix64 word, r = lo + hi x^2 mod r."""
+    """bgv_calls.cpp debug_slots (bgv_debug_prepare): the i-th nonzero splitmix64 word, r = lo + hi x^2 mod r."""
     out, st = [], seed
     while len(out) < n:
         st, w = splitmix64(st)
