@@ -191,6 +191,42 @@ int bgv_shuffling_put(bgv_ctx* ctx, uint32_t first_id, const uint8_t seed[32], c
                       uint32_t* out_shuffling);
 int bgv_committee_drop_range(bgv_ctx* ctx, uint32_t first_id, uint32_t count);
 
+/* Balance-weighted sampling on the device: computeProposerIndex and getNextSyncCommittee
+ * (state-transition/src/util/seed.ts:22-126, util/syncCommittee.ts:21-38).  For a 32-byte seed,
+ * n_active active indices and candidate i = 0, 1, 2, ...:
+ *   v_i    = active_indices[compute_shuffled_index(i mod n_active, n_active, seed)]  (rounds rounds,
+ *            as bgv_shuffling_put)
+ *   byte_i = sha256(seed | LE64(i div 32))[i mod 32]
+ *   candidate i is accepted iff eff_incr[v_i] * 255 >= max_incr * byte_i
+ * eff_incr is EffectiveBalanceIncrements (one byte per validator index, n_eff of them) and max_incr
+ * the preset's MAX_EFFECTIVE_BALANCE / EFFECTIVE_BALANCE_INCREMENT.  At most BGV_SAMPLE_MAX_TRIES
+ * candidates of a seed are examined, which bounds every call.
+ *
+ * bgv_proposers: out_proposers[s] = the first accepted v_i of seeds32[32 s ..), for n_seeds seeds
+ * (1..1024; the caller hashes epochSeed | LE64(slot) per slot as computeProposers does), or
+ * BGV_NO_PROPOSER when all n_active candidates were rejected (the reference's -1).  The pubkey
+ * cache is not involved.  -BGV_E_ARG, and nothing written: a null pointer, n_seeds out of range,
+ * n_active 0 or > 2^22, rounds > 255, max_incr 0 or > 255, an active index >= n_eff, or a seed whose
+ * first BGV_SAMPLE_MAX_TRIES candidates were all rejected while n_active is larger than that.
+ *
+ * bgv_sync_committee_put: the first `size` accepted v_i (1..65536; in order, repeats kept: i runs
+ * past n_active) become committee `id`, a committee in every respect exactly as after a
+ * bgv_committee_put of the same list.  out_indices (may be NULL) receives the list, out_agg48 (may
+ * be NULL) the members' pubkey sum, repeats counted, as 48 compressed bytes
+ * (SyncCommittee.aggregatePubkey).  -BGV_E_ARG: the argument checks above, an id that is live or
+ * >= BGV_MAX_COMMITTEES, or fewer than `size` acceptances within BGV_SAMPLE_MAX_TRIES candidates
+ * (where the reference's loop would go on; a zero balance is accepted on a random byte of 0
+ * only); -BGV_E_BAD_INDEX: an active index at or past
+ * bgv_pubkeys_count, or a marked one.  All or nothing: on any error the id does not exist. */
+#define BGV_NO_PROPOSER 0xFFFFFFFFu
+#define BGV_SAMPLE_MAX_TRIES 65536u
+int bgv_proposers(bgv_ctx* ctx, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active_indices,
+                  size_t n_active, const uint8_t* eff_incr, size_t n_eff, uint32_t max_incr, uint32_t rounds,
+                  uint32_t* out_proposers);
+int bgv_sync_committee_put(bgv_ctx* ctx, uint32_t id, const uint8_t seed[32], const uint32_t* active_indices,
+                           size_t n_active, const uint8_t* eff_incr, size_t n_eff, uint32_t max_incr, uint32_t size,
+                           uint32_t rounds, uint32_t* out_indices, uint8_t out_agg48[48]);
+
 /* The pubkeys of one set as committee members: member k takes part iff
  * (bits[k >> 3] >> (k & 7)) & 1 (SSZ bit order); bits holds ceil(n_bits / 8) bytes.
  * committee == BGV_NO_COMMITTEE: the set's own pk_indices / pk_bytes count. */

@@ -1,6 +1,8 @@
-// libblsgpu: the device-resident registries: the pubkey cache, committees, epoch shuffling and keygen.
+// libblsgpu: the device-resident registries: the pubkey cache, committees, epoch shuffling, sampling and keygen.
 #include "bgv_ctx.h"
+#include "bgv_sample.h"   // balance-weighted sampling (bgv_proposers, bgv_sync_committee_put)
 #include "bgv_shuffle.h"  // the committee bounds of an epoch shuffling (bgv_shuffling_put)
+#include "bls_constants.h"
 
 extern "C" {
 
@@ -89,9 +91,9 @@ static int com_pool_grow(bgv_ctx* c, size_t need) {
   return BGV_OK;
 }
 
-int bgv_committee_put(bgv_ctx* c, uint32_t id, const uint32_t* indices, size_t n) {
-  if (!c || id >= BGV_MAX_COMMITTEES || !indices || n < 1 || n > 65536) return -BGV_E_ARG;
-  std::lock_guard<std::mutex> plk(c->put_mu);
+// bgv_committee_put under put_mu (the caller's): the checks, a handle and a pool range, the list
+// and its sum on every device, then the id.  bgv_sync_committee_put stores its picks through it.
+static int committee_put_locked(bgv_ctx* c, uint32_t id, const uint32_t* indices, size_t n) {
   auto rec = std::make_shared<CommitteeRec>();
   // the checks, then the upload into a handle and a pool range no laid-out call names, and the
   // sum; under the shared cache lock (verifies go on) unless the pool has to grow
@@ -144,9 +146,14 @@ int bgv_committee_put(bgv_ctx* c, uint32_t id, const uint32_t* indices, size_t n
   return upload();
 }
 
-int bgv_committee_drop(bgv_ctx* c, uint32_t id) {
-  if (!c) return -BGV_E_ARG;
+int bgv_committee_put(bgv_ctx* c, uint32_t id, const uint32_t* indices, size_t n) {
+  if (!c || id >= BGV_MAX_COMMITTEES || !indices || n < 1 || n > 65536) return -BGV_E_ARG;
   std::lock_guard<std::mutex> plk(c->put_mu);
+  return committee_put_locked(c, id, indices, n);
+}
+
+// bgv_committee_drop under put_mu (the caller's)
+static int committee_drop_locked(bgv_ctx* c, uint32_t id) {
   if (c->closed) return -BGV_E_CLOSED;
   std::shared_ptr<CommitteeRec> rec;  // released after com_mu: the last reference frees the handle
   std::unique_lock<std::shared_mutex> lk(c->com_mu);
@@ -159,6 +166,12 @@ int bgv_committee_drop(bgv_ctx* c, uint32_t id) {
                    c->retired.end());
   c->retired.push_back(rec);
   return BGV_OK;
+}
+
+int bgv_committee_drop(bgv_ctx* c, uint32_t id) {
+  if (!c) return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  return committee_drop_locked(c, id);
 }
 
 // An epoch's committees in one call: the device shuffles the active indices straight into one
@@ -279,6 +292,168 @@ int bgv_committee_drop_range(bgv_ctx* c, uint32_t first_id, uint32_t count) {
     c->committees.erase(it);
   }
   return (int)recs.size();
+}
+
+}  // extern "C"
+
+static_assert(BGV_SAMPLE_CAP == BGV_SAMPLE_MAX_TRIES, "bgv_sample.h plans its passes within the public cap");
+
+namespace {
+// samp_run's device: one pass is k_sample_eval + k_sample_pick over the seeds still short, on the
+// utility stream, and one synchronize that reads the seeds' states back.
+struct SampleDev {
+  Device& d;
+  DevScope<>& sc;
+  bgv_sample_in in;
+  uint32_t n_seeds;
+  uint32_t* todo = nullptr;  // n_seeds words
+  uint32_t* vals = nullptr;  // one pass's results: cap candidates
+  uint8_t* flags = nullptr;
+  size_t cap = 0;
+  int pass(const std::vector<uint32_t>& todo_h, const samp_pass& p, std::vector<samp_state>& st) {
+    const size_t items = todo_h.size() * (size_t)p.window;
+    if (items > cap) {  // the smaller ones stay with the scope until the call ends
+      if (sc.alloc(&vals, items) || sc.alloc(&flags, items)) return -BGV_E_DEVICE;
+      cap = items;
+    }
+    sc.enqueued();  // the stream reads todo_h and writes st
+    HIPCHK(hipMemcpyAsync(todo, todo_h.data(), 4 * todo_h.size(), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(bgv_launch_sample_pass(in, todo, (uint32_t)todo_h.size(), p.window, p.count, vals, flags, d.stream));
+    HIPCHK(hipMemcpyAsync(st.data(), in.state, sizeof(samp_state) * n_seeds, hipMemcpyDeviceToHost, d.stream));
+    return sc.sync();
+  }
+};
+
+bool sample_args_ok(const uint32_t* active, size_t n_active, const uint8_t* eff, size_t n_eff, uint32_t max_incr,
+                    uint32_t rounds) {
+  if (!active || !eff || n_active < 1 || n_active > BGV_SHUFFLE_MAX_N || n_eff < 1 || n_eff > (size_t)UINT32_MAX ||
+      rounds > BGV_SHUFFLE_MAX_ROUNDS || max_incr < 1 || max_incr > 255)
+    return false;
+  for (size_t i = 0; i < n_active; ++i)
+    if (active[i] >= n_eff) return false;
+  return true;
+}
+
+// The first `want` accepted candidates of each seed, sampled on the first device: st[s].have of
+// them at picks[s * want ..).  Under the shared cache_mu (the devices stay); takes util_mu.
+int sample_run(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, uint32_t n,
+               const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t rounds, uint32_t want, uint32_t limit,
+               std::vector<samp_state>& st, std::vector<uint32_t>& picks) {
+  std::vector<shuf_seed> seeds(n_seeds);
+  for (uint32_t s = 0; s < n_seeds; ++s) seeds[s] = shuf_seed_load(seeds32 + 32 * (size_t)s);
+  picks.assign((size_t)n_seeds * want, 0);
+  std::lock_guard<std::mutex> ulk(c->util_mu);
+  Device& d = c->devs[0];
+  HIPCHK(hipSetDevice(d.id));
+  DevScope<> sc(d.stream);
+  shuf_seed* dseeds = nullptr;
+  samp_state* dstate = nullptr;
+  uint32_t *dact = nullptr, *dpicks = nullptr, *dtodo = nullptr;
+  uint8_t* deff = nullptr;
+  if (sc.alloc(&dseeds, n_seeds) || sc.alloc(&dstate, n_seeds) || sc.alloc(&dact, n) || sc.alloc(&deff, n_eff) ||
+      sc.alloc(&dpicks, picks.size()) || sc.alloc(&dtodo, n_seeds))
+    return -BGV_E_DEVICE;
+  HIPCHK(hipMemcpyAsync(dseeds, seeds.data(), sizeof(shuf_seed) * n_seeds, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemsetAsync(dstate, 0, sizeof(samp_state) * n_seeds, d.stream));
+  HIPCHK(hipMemcpyAsync(dact, active, 4 * (size_t)n, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(deff, eff, n_eff, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemsetAsync(dpicks, 0, 4 * picks.size(), d.stream));
+  const bgv_sample_in in{dseeds, dstate, dact, n, deff, max_incr, rounds, limit, want, dpicks};
+  SampleDev dev{d, sc, in, n_seeds, dtodo};
+  if (int rc = samp_run(dev, n_seeds, want, limit, st)) return rc;
+  sc.enqueued();
+  HIPCHK(hipMemcpyAsync(picks.data(), dpicks, 4 * picks.size(), hipMemcpyDeviceToHost, d.stream));
+  return sc.sync();
+}
+
+// 96-byte uncompressed G1 record (x | y big-endian, 0x40 for infinity) to the 48 compressed bytes
+void g1_compress(uint8_t out48[48], const uint8_t in96[96]) {
+  if (in96[0] & 0x40) {
+    memset(out48, 0, 48);
+    out48[0] = 0xC0;
+    return;
+  }
+  static const uint32_t half[12] = BGV_EXP_P_MINUS_1_DIV_2;  // (p - 1) / 2, little-endian words
+  int cmp = 0;  // y against it, from the top byte down
+  for (int k = 0; k < 48 && cmp == 0; ++k) {
+    const uint8_t h = (uint8_t)(half[11 - k / 4] >> (24 - 8 * (k % 4)));
+    cmp = in96[48 + k] > h ? 1 : in96[48 + k] < h ? -1 : 0;
+  }
+  memcpy(out48, in96, 48);
+  out48[0] |= cmp > 0 ? 0xA0 : 0x80;
+}
+}  // namespace
+
+extern "C" {
+
+int bgv_proposers(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, size_t n_active,
+                  const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t rounds, uint32_t* out_proposers) {
+  if (!c || !seeds32 || !out_proposers || n_seeds < 1 || n_seeds > BGV_SAMPLE_MAX_SEEDS ||
+      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds))
+    return -BGV_E_ARG;
+  const uint32_t limit = samp_limit(n_active, true);
+  std::vector<samp_state> st;
+  std::vector<uint32_t> picks;
+  {
+    std::shared_lock<std::shared_mutex> clk(c->cache_mu);  // bgv_close frees the devices under the exclusive lock
+    if (c->closed) return -BGV_E_CLOSED;
+    if (int rc = sample_run(c, seeds32, n_seeds, active, (uint32_t)n_active, eff, n_eff, max_incr, rounds, 1, limit, st,
+                            picks))
+      return rc;
+  }
+  // every candidate rejected: the reference's -1 when that was the whole list, else the cap was hit
+  for (uint32_t s = 0; s < n_seeds; ++s)
+    if (!st[s].have && n_active > limit) return -BGV_E_ARG;
+  for (uint32_t s = 0; s < n_seeds; ++s) out_proposers[s] = st[s].have ? picks[s] : BGV_NO_PROPOSER;
+  return BGV_OK;
+}
+
+// The next sync committee: sampled on the first device, then stored on every device exactly as
+// bgv_committee_put stores a list (committee_put_locked: checks, pool range, directory entry,
+// k_committee_total).  put_mu is held throughout, so neither the cache nor the id changes between
+// the sampling and the store; the aggregate is read through bgv_aggregate_committee_bits once
+// the committee exists, and the id is dropped again should that fail.
+int bgv_sync_committee_put(bgv_ctx* c, uint32_t id, const uint8_t seed[32], const uint32_t* active, size_t n_active,
+                           const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t size, uint32_t rounds,
+                           uint32_t* out_indices, uint8_t out_agg48[48]) {
+  if (!c || !seed || id >= BGV_MAX_COMMITTEES || size < 1 || size > BGV_SAMPLE_MAX_WANT ||
+      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds))
+    return -BGV_E_ARG;
+  std::lock_guard<std::mutex> plk(c->put_mu);
+  std::vector<samp_state> st;
+  std::vector<uint32_t> picks;
+  {
+    std::shared_lock<std::shared_mutex> clk(c->cache_mu);
+    if (c->closed) return -BGV_E_CLOSED;
+    {
+      std::shared_lock<std::shared_mutex> lk(c->com_mu);
+      if (c->committees.count(id)) return -BGV_E_ARG;
+    }
+    const size_t npk = c->n_pubkeys;
+    const bool marks = !c->bad_pk.empty();
+    for (size_t i = 0; i < n_active; ++i)
+      if (active[i] >= npk || (marks && c->bad_pk.count(active[i]))) return -BGV_E_BAD_INDEX;
+    if (int rc = sample_run(c, seed, 1, active, (uint32_t)n_active, eff, n_eff, max_incr, rounds, size,
+                            samp_limit(n_active, false), st, picks))
+      return rc;
+    if (st[0].have < size) return -BGV_E_ARG;  // the cap
+  }
+  if (int rc = committee_put_locked(c, id, picks.data(), size)) return rc;
+  if (out_agg48) {
+    const std::vector<uint8_t> bits = [&] {
+      std::vector<uint8_t> b((size + 7) / 8, 0xff);
+      if (size % 8) b.back() = (uint8_t)((1u << (size % 8)) - 1u);
+      return b;
+    }();
+    uint8_t agg96[96];
+    if (int rc = bgv_aggregate_committee_bits(c, id, bits.data(), size, agg96)) {
+      (void)committee_drop_locked(c, id);
+      return rc;
+    }
+    g1_compress(out_agg48, agg96);
+  }
+  if (out_indices) memcpy(out_indices, picks.data(), 4 * (size_t)size);
+  return BGV_OK;
 }
 
 namespace {

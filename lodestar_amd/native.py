@@ -36,6 +36,8 @@ PK_COMPRESSED = 48
 PK_UNCOMPRESSED = 96
 MAX_COMMITTEES = 16384
 NO_COMMITTEE = 0xFFFFFFFF
+NO_PROPOSER = 0xFFFFFFFF
+SAMPLE_MAX_TRIES = 65536
 
 EXPORTED_SYMBOLS = [
     "bgv_init", "bgv_close", "bgv_destroy", "bgv_pubkeys_put", "bgv_pubkeys_count", "bgv_verify",
@@ -45,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "bgv_verify_partial", "bgv_final_verify", "bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split",
     "bgv_committee_put", "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
     "bgv_aggregate_committee_bits", "bgv_shuffling_put", "bgv_committee_drop_range",
+    "bgv_proposers", "bgv_sync_committee_put",
 ]
 
 
@@ -129,12 +132,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_aggregate_committee_bits": ([P, U32, P, U32, P], ctypes.c_int),
             "bgv_shuffling_put": ([P, U32, P, P, SZ, U32, U32, U32, P], ctypes.c_int),
             "bgv_committee_drop_range": ([P, U32, U32], ctypes.c_int),
+            "bgv_proposers": ([P, P, U32, P, SZ, P, SZ, U32, U32, P], ctypes.c_int),
+            "bgv_sync_committee_put": ([P, U32, P, P, SZ, P, SZ, U32, U32, U32, P, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
                         "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
                         "bgv_aggregate_committee_bits", "bgv_shuffling_put",
-                        "bgv_committee_drop_range") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_committee_drop_range", "bgv_proposers", "bgv_sync_committee_put") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -265,6 +270,35 @@ class Context:
         _check(self.lib.bgv_shuffling_put(self._h, first_id, _buf(bytes(seed)), act.ctypes.data, act.size, slots,
                                           committees_per_slot, rounds, out.ctypes.data))
         return out[:act.size]
+
+    def proposers(self, seeds: Sequence[bytes], active_indices: Sequence[int], eff_incr: bytes, max_incr: int = 32,
+                  rounds: int = 90) -> list:
+        """computeProposerIndex for every 32-byte seed in one call (bgv_proposers): the first
+        candidate of each seed accepted by its effective balance (eff_incr: one byte per validator
+        index), None where all len(active_indices) candidates were rejected."""
+        import numpy as np
+        assert all(len(s) == 32 for s in seeds)
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        eff = np.frombuffer(bytes(eff_incr), dtype=np.uint8)
+        out = np.empty(max(1, len(seeds)), dtype=np.uint32)
+        _check(self.lib.bgv_proposers(self._h, _buf(b"".join(seeds)), len(seeds), act.ctypes.data, act.size,
+                                      eff.ctypes.data, eff.size, max_incr, rounds, out.ctypes.data))
+        return [None if v == NO_PROPOSER else int(v) for v in out[:len(seeds)]]
+
+    def sync_committee_put(self, committee_id: int, seed: bytes, active_indices: Sequence[int], eff_incr: bytes,
+                           max_incr: int = 32, size: int = 512, rounds: int = 90):
+        """getNextSyncCommittee in one call (bgv_sync_committee_put): the first `size` candidates
+        accepted by balance, repeats kept, become committee committee_id on every device.  Returns
+        (indices as a numpy uint32 array, the 48-byte compressed aggregate pubkey)."""
+        import numpy as np
+        assert len(seed) == 32
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        eff = np.frombuffer(bytes(eff_incr), dtype=np.uint8)
+        out = np.empty(max(1, size), dtype=np.uint32)
+        agg = ctypes.create_string_buffer(48)
+        _check(self.lib.bgv_sync_committee_put(self._h, committee_id, _buf(bytes(seed)), act.ctypes.data, act.size,
+                                               eff.ctypes.data, eff.size, max_incr, size, rounds, out.ctypes.data, agg))
+        return out[:size], agg.raw
 
     def committee_drop_range(self, first_id: int, count: int) -> int:
         """Drop the live committees of ids first_id .. first_id + count - 1; returns how many."""

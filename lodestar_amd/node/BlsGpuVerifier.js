@@ -17,6 +17,7 @@
  * per-call device time stands in for the worker job time.  latencyToWorker/FromWorker
  * (structured-clone messaging) have no GPU counterpart and are not observed.
  */
+const crypto = require("crypto");
 const path = require("path");
 const addon = require(path.join(__dirname, "blsgpu.node"));
 
@@ -39,7 +40,9 @@ const MAX_BUFFER_WAIT_MS = 1;
 // the participation bitfield
 const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee"};
 const PUBKEY_RUN = 8192;
+const NO_PROPOSER = 0xffffffff; // BGV_NO_PROPOSER
 // include/blsgpu.h: BGV_BLST_* decode statuses are 1..19 (library codes start at 20)
+const toUint8Array = (v) => (v instanceof Uint8Array ? v : Uint8Array.from(v));
 const isBlstDecodeCode = (code) => typeof code === "number" && code <= -1 && code >= -19;
 
 // One contiguous run of queued validator keys: indices [first, first + n), their 48-byte
@@ -286,6 +289,42 @@ class BlsGpuVerifier {
     await this.flushPubkeys();
     const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
     return addon.shufflingPut(this.ctx, firstId, seed, active, slots, committeesPerSlot, rounds);
+  }
+
+  /**
+   * The proposers of `slots` slots from startSlot on (computeProposers, util/seed.ts:22-39) in one
+   * device call: the per-slot seeds sha256(epochSeed | LE64(slot)) are hashed here, the balance-
+   * weighted sampling (computeProposerIndex) runs on the device off the event loop.  Resolves to a
+   * number[] with -1 where every candidate was rejected, as the reference.  The pubkey cache is
+   * not involved.
+   */
+  async computeProposers(epochSeed, startSlot, activeIndices, effectiveBalanceIncrements, opts) {
+    const {slots, maxEffectiveBalanceIncrement, rounds} = opts;
+    const seeds = new Uint8Array(32 * slots);
+    const msg = Buffer.alloc(40);
+    Buffer.from(epochSeed.buffer, epochSeed.byteOffset, epochSeed.byteLength).copy(msg, 0, 0, 32);
+    for (let k = 0; k < slots; k++) {
+      msg.writeBigUInt64LE(BigInt(startSlot + k), 32);
+      seeds.set(crypto.createHash("sha256").update(msg).digest(), 32 * k);
+    }
+    const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+    const eff = toUint8Array(effectiveBalanceIncrements);
+    const out = await addon.proposers(this.ctx, seeds, active, eff, maxEffectiveBalanceIncrement, rounds);
+    return Array.from(out, (v) => (v === NO_PROPOSER ? -1 : v));
+  }
+
+  /**
+   * The next sync committee in one device call (getNextSyncCommittee, util/syncCommittee.ts:21-38;
+   * INTEGRATION.md §2c): the first `size` candidates accepted by balance become committee `id`,
+   * repeats kept, on every device, exactly as after committeePut of the same list.  Resolves to
+   * {indices: Uint32Array, aggregatePubkey: Uint8Array(48)}.  The queued pubkeys go first.
+   */
+  async syncCommitteePut(id, seed, activeIndices, effectiveBalanceIncrements, opts) {
+    const {size, maxEffectiveBalanceIncrement, rounds} = opts;
+    await this.flushPubkeys();
+    const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
+    const eff = toUint8Array(effectiveBalanceIncrements);
+    return addon.syncCommitteePut(this.ctx, id, seed, active, eff, maxEffectiveBalanceIncrement, size, rounds);
   }
 
   /** Drops the live ids of firstId .. firstId + count - 1 (an epoch's committees); returns how many. */

@@ -486,6 +486,132 @@ static napi_value js_shuffling_put(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* proposers(ctx, seeds: Uint8Array(32 k), activeIndices: Uint32Array, effectiveBalanceIncrements:
+ * Uint8Array, maxIncr, rounds) -> Promise<Uint32Array(k)> (bgv_proposers; 0xFFFFFFFF: no proposer)
+ * and syncCommitteePut(ctx, id, seed: Uint8Array(32), activeIndices, effectiveBalanceIncrements,
+ * maxIncr, size, rounds) -> Promise<{indices: Uint32Array(size), aggregatePubkey: Uint8Array(48)}>
+ * (bgv_sync_committee_put), both on a libuv pool thread like shufflingPut and rejecting with an
+ * Error whose .bgvCode is the negative library code. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  napi_ref ctx_ref, seed_ref, act_ref, eff_ref, out_ref, agg_ref;
+  bgv_ctx* c;
+  int sync; /* syncCommitteePut, else proposers */
+  uint32_t id, n_seeds, max_incr, size, rounds;
+  const uint8_t *seeds, *eff;
+  const uint32_t* active;
+  size_t n, n_eff;
+  uint32_t* out;
+  uint8_t* agg;
+  int rc;
+} samp_req;
+
+static void samp_execute(napi_env env, void* data) {
+  (void)env;
+  samp_req* r = (samp_req*)data;
+  if (r->sync)
+    r->rc = bgv_sync_committee_put(r->c, r->id, r->seeds, r->active, r->n, r->eff, r->n_eff, r->max_incr, r->size,
+                                   r->rounds, r->out, r->agg);
+  else
+    r->rc = bgv_proposers(r->c, r->seeds, r->n_seeds, r->active, r->n, r->eff, r->n_eff, r->max_incr, r->rounds,
+                          r->out);
+}
+
+static void samp_complete(napi_env env, napi_status status, void* data) {
+  samp_req* r = (samp_req*)data;
+  napi_value out, agg, res;
+  int ok = status == napi_ok && r->rc == 0 && napi_get_reference_value(env, r->out_ref, &out) == napi_ok;
+  if (ok && r->sync) {
+    ok = napi_get_reference_value(env, r->agg_ref, &agg) == napi_ok && napi_create_object(env, &res) == napi_ok &&
+         napi_set_named_property(env, res, "indices", out) == napi_ok &&
+         napi_set_named_property(env, res, "aggregatePubkey", agg) == napi_ok;
+    out = res;
+  }
+  if (ok) {
+    napi_resolve_deferred(env, r->deferred, out);
+  } else {
+    const int rc = status == napi_ok && r->rc ? r->rc : -BGV_E_ARG;
+    napi_value msg, err, code;
+    napi_create_string_utf8(env, bgv_strerror(rc), NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int32(env, rc, &code);
+    napi_set_named_property(env, err, "bgvCode", code);
+    napi_reject_deferred(env, r->deferred, err);
+  }
+  napi_delete_reference(env, r->ctx_ref);
+  napi_delete_reference(env, r->seed_ref);
+  napi_delete_reference(env, r->act_ref);
+  napi_delete_reference(env, r->eff_ref);
+  napi_delete_reference(env, r->out_ref);
+  if (r->agg_ref) napi_delete_reference(env, r->agg_ref);
+  napi_delete_async_work(env, r->work);
+  free(r);
+}
+
+/* argv[0] the context, then for sync [id, seed, active, eff, maxIncr, size, rounds], else
+ * [seeds, active, eff, maxIncr, rounds] */
+static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
+  size_t argc = 8;
+  napi_value argv[8], promise, name, ab, out, agg = NULL;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  const size_t a = sync ? 2 : 1; /* where the seeds are */
+  uint8_t *seeds, *act, *eff;
+  size_t seeds_len, act_len, eff_len;
+  uint32_t id = 0, max_incr = 0, size = 0, rounds = 0;
+  napi_typedarray_type act_type, eff_type;
+  if (argc < (sync ? 8u : 6u) || (sync && napi_get_value_uint32(env, argv[1], &id) != napi_ok) ||
+      get_bytes(env, argv[a], &seeds, &seeds_len) || seeds_len == 0 || seeds_len % 32 || (sync && seeds_len != 32) ||
+      get_bytes(env, argv[a + 1], &act, &act_len) || act_len == 0 ||
+      napi_get_typedarray_info(env, argv[a + 1], &act_type, NULL, NULL, NULL, NULL) != napi_ok ||
+      act_type != napi_uint32_array || get_bytes(env, argv[a + 2], &eff, &eff_len) || eff_len == 0 ||
+      napi_get_typedarray_info(env, argv[a + 2], &eff_type, NULL, NULL, NULL, NULL) != napi_ok ||
+      eff_type != napi_uint8_array || napi_get_value_uint32(env, argv[a + 3], &max_incr) != napi_ok ||
+      (sync && napi_get_value_uint32(env, argv[a + 4], &size) != napi_ok) ||
+      napi_get_value_uint32(env, argv[sync ? 7 : 5], &rounds) != napi_ok || (sync && (size < 1 || size > 65536)) ||
+      seeds_len / 32 > 1024)
+    return throw_code(env, -BGV_E_ARG);
+  const size_t n_out = sync ? size : seeds_len / 32;
+  void *dst, *agg_dst = NULL;
+  CHECK(env, napi_create_arraybuffer(env, 4 * n_out, &dst, &ab));
+  CHECK(env, napi_create_typedarray(env, napi_uint32_array, n_out, ab, 0, &out));
+  if (sync && !(agg = new_bytes(env, 48, &agg_dst))) return throw_code(env, -BGV_E_ARG);
+  samp_req* r = (samp_req*)calloc(1, sizeof(samp_req));
+  r->c = ctx;
+  r->sync = sync;
+  r->id = id;
+  r->n_seeds = (uint32_t)(seeds_len / 32);
+  r->max_incr = max_incr;
+  r->size = size;
+  r->rounds = rounds;
+  r->seeds = seeds;
+  r->active = (const uint32_t*)act;
+  r->n = act_len / 4;
+  r->eff = eff;
+  r->n_eff = eff_len;
+  r->out = (uint32_t*)dst;
+  r->agg = (uint8_t*)agg_dst;
+  if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
+      napi_create_reference(env, argv[0], 1, &r->ctx_ref) != napi_ok ||
+      napi_create_reference(env, argv[a], 1, &r->seed_ref) != napi_ok ||
+      napi_create_reference(env, argv[a + 1], 1, &r->act_ref) != napi_ok ||
+      napi_create_reference(env, argv[a + 2], 1, &r->eff_ref) != napi_ok ||
+      napi_create_reference(env, out, 1, &r->out_ref) != napi_ok ||
+      (sync && napi_create_reference(env, agg, 1, &r->agg_ref) != napi_ok) ||
+      napi_create_string_utf8(env, sync ? "blsgpu.syncCommitteePut" : "blsgpu.proposers", NAPI_AUTO_LENGTH, &name) !=
+          napi_ok ||
+      napi_create_async_work(env, NULL, name, samp_execute, samp_complete, r, &r->work) != napi_ok ||
+      napi_queue_async_work(env, r->work) != napi_ok) {
+    napi_throw_error(env, NULL, "blsgpu: N-API failure");
+    return NULL;
+  }
+  return promise;
+}
+
+static napi_value js_proposers(napi_env env, napi_callback_info info) { return samp_start(env, info, 0); }
+static napi_value js_sync_committee_put(napi_env env, napi_callback_info info) { return samp_start(env, info, 1); }
+
 /* aggregateCommitteeBits(ctx, id, bits: Uint8Array, nBits) -> Uint8Array(96): the aggregate of the
  * committee members whose bit is set, through the verify path's kernel (parity hook). */
 static napi_value js_aggregate_committee_bits(napi_env env, napi_callback_info info) {
@@ -872,6 +998,8 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeeDropRange", NULL, js_committee_drop_range, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"shufflingPut", NULL, js_shuffling_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"proposers", NULL, js_proposers, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"syncCommitteePut", NULL, js_sync_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregateCommitteeBits", NULL, js_aggregate_committee_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"hashToG2", NULL, js_hash_to_g2, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"pubkeysValidate", NULL, js_pubkeys_validate, NULL, NULL, NULL, METHOD_ATTR, NULL},

@@ -98,6 +98,28 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     committeesPerSlot: number,
     rounds: number
   ): Promise<Uint32Array>;
+  /**
+   * computeProposers on the device: the proposers of opts.slots slots from startSlot on, -1 where
+   * every candidate was rejected; the per-slot seeds are hashed here
+   */
+  computeProposers(
+    epochSeed: Uint8Array,
+    startSlot: number,
+    activeIndices: Uint32Array | number[],
+    effectiveBalanceIncrements: Uint8Array,
+    opts: {slots: number; maxEffectiveBalanceIncrement: number; rounds: number}
+  ): Promise<number[]>;
+  /**
+   * getNextSyncCommittee on the device: the first opts.size candidates accepted by balance (repeats
+   * kept) become committee id; resolves to the list and its 48-byte aggregate pubkey
+   */
+  syncCommitteePut(
+    id: number,
+    seed: Uint8Array,
+    activeIndices: Uint32Array | number[],
+    effectiveBalanceIncrements: Uint8Array,
+    opts: {size: number; maxEffectiveBalanceIncrement: number; rounds: number}
+  ): Promise<{indices: Uint32Array; aggregatePubkey: Uint8Array}>;
   /** drops the live ids of firstId .. firstId + count - 1; returns how many there were */
   committeeDropRange(firstId: number, count: number): number;
   onPubkeyError: ((e: Error, first: number, n: number) => void) | null;
