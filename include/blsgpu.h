@@ -290,7 +290,7 @@ int bgv_final_verify(bgv_ctx* ctx, const uint8_t* partials, size_t n, int32_t* o
 /* Parity hook (tests only): the per-set intermediates of a verify call's kernels with the
  * path forced, so the latency path (which serves every call of up to 16,384 pairs: gossip,
  * block import) is checked byte for byte against the bulk path and the hash_to_G2 goldens.
- *   path 1 (BGV_PATH_BULK)     k_prep (task_hash/task_sig/task_pk), k_miller one pair per lane
+ *   path 1 (BGV_PATH_BULK)     k_prep (task_hash/task_sig/task_pk), k_lines + k_facc one pair per lane
  *   path 2 (BGV_PATH_LATENCY)  k_prep_a + k_prep_team, k_miller_team
  * The n sets (cached pubkeys only) form one job in groups of 64; set i gets the i-th nonzero
  * splitmix64 output from `seed` as its randomizer, so both paths see the same r_i.

@@ -164,45 +164,36 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   final12_body(groups, ngroups, f, gpair, verdict, gprod, gu, gu1, gpkp);
 }
 
-// The latency path's closing (small calls): one block of BGV_FOLD_TEAMS (16) teams per group.
-// Team t multiplies the group's slots t, t + 16, ... (team 0 also the signature pair), the
-// partial products meet in LDS in a four-level tree (a sixteenth of k_final's serial product
-// chain; 8 teams measured 0.86 ms for the 64-set gossip call).  The final exponentiation then runs on the
-// whole block with each coefficient's products split over eight lanes (tm_wide_ops_t<false, 8>):
-// one double-width product per lane for a squaring (two for a product) instead of 7 on one.
-// ENGINE 2 (round 6, the default k_final_fold): the final exponentiation in residue arithmetic
-// (bgv_rns.h) on a 384-thread block, one residue of one coefficient per lane and one Montgomery
-// reduction (two base extensions) per coefficient and operation: 0.96 against 1.89 us per Fp12
-// operation of the eight-part engine (tools/ubench_rns.hip, profiles/r06/rns/); the fold keeps
-// its 16 teams, the block's other 128 threads (teams 16..23) run the same products on ones so
-// every thread reaches every barrier.  ENGINE 1 (k_final_fold_p8, BGV_FOLD_RNS=0): the
-// eight-part engine with the lane's squaring recipes (bgv_team_dev.h tm_wide8_lean_ops);
-// ENGINE 0 (k_final_fold_sel, BGV_FOLD_RNS=0 BGV_FOLD_LEAN=0) its select-based forms.  The same
-// field elements every way: u, the verdict bits and gu agree.
-}  // extern "C"
-template <bool LEAN>
-__device__ auto bgv_fold_ops_pick() {
-  if constexpr (LEAN)
-    return tm_wide8_lean_ops{};
-  else
-    return tm_wide_ops_t<false, 8>{};
-}
+// The closing of the latency path (small calls) and of small uniform retry rounds: one block of
+// BGV_FOLD_RNS_THREADS (384) threads per group.  Its first BGV_FOLD_TEAMS (16) teams fold the
+// group: team t multiplies the group's slots t, t + 16, ... (team 0 also the signature pair), and
+// the partial products meet in LDS in a four-level tree (a sixteenth of k_final's serial product
+// chain; 8 teams measured 0.86 ms for the 64-set gossip call).  The block's other 128 threads
+// (teams 16..23) run the same products on ones, so every thread reaches every barrier.  The
+// final exponentiation then runs on the whole block in residue arithmetic (bgv_rns.h): one
+// residue of one coefficient per lane, one Montgomery reduction (two base extensions) per
+// coefficient and operation, 0.96 us per Fp12 operation against 1.89 us for the eight-part
+// positional engine it replaced (tools/ubench_rns.hip, profiles/r06/rns/).  The same field
+// elements as k_final12: u, the verdict bits and gu agree.
 #ifndef BGV_FOLD_TEAMS
-#define BGV_FOLD_TEAMS 16  // 16-lane teams of k_final_fold's fold (BGV_FOLD_THREADS threads)
+#define BGV_FOLD_TEAMS 16  // 16-lane teams of k_final_fold's fold
 #endif
-#define BGV_FOLD_THREADS (BGV_FOLD_TEAMS * BGV_TEAM)
 #define BGV_FOLD_RNS_THREADS BGV_RNS_THREADS
-static_assert(BGV_FOLD_RNS_THREADS % BGV_TEAM == 0 && BGV_FOLD_RNS_THREADS >= BGV_FOLD_THREADS, "fold block");
-template <int ENGINE>
-__device__ __forceinline__ void final_fold_body(const bgv_dgroup* __restrict__ groups, uint32_t ngroups,
-                                                const fp12_t* __restrict__ f, const fp12_t* __restrict__ gpair,
-                                                int32_t* __restrict__ verdict, fp12_t* __restrict__ gprod,
-                                                fp12_t* __restrict__ gu, const fp12_t* __restrict__ gu1,
-                                                const fp12_t* __restrict__ fsig, const fp12_t* __restrict__ gpkp) {
-  constexpr int kTeams = (ENGINE == 2 ? BGV_FOLD_RNS_THREADS : BGV_FOLD_THREADS) / BGV_TEAM;
+static_assert(BGV_FOLD_RNS_THREADS % BGV_TEAM == 0 && BGV_FOLD_RNS_THREADS >= BGV_FOLD_TEAMS * BGV_TEAM, "fold block");
+#define BGV_FOLD_ARGS                                                                                         \
+  const bgv_dgroup *__restrict__ groups, uint32_t ngroups, const fp12_t *__restrict__ f,                     \
+      const fp12_t *__restrict__ gpair, int32_t *__restrict__ verdict, fp12_t *__restrict__ gprod,          \
+      fp12_t *__restrict__ gu, const fp12_t *__restrict__ gu1, const fp12_t *__restrict__ fsig,                \
+      const fp12_t *__restrict__ gpkp
+}  // extern "C"
+// The kernel's body, inlined into it from a function of its own as final12_body is: with the same
+// statements written straight into the kernel the compiler orders two loads and their waits
+// differently, and config 3's p50 read 2.35-2.37 against 2.34-2.35 ms (profiles/retire_ab/).
+__device__ __forceinline__ void final_fold_body(BGV_FOLD_ARGS) {
+  constexpr int kTeams = BGV_FOLD_RNS_THREADS / BGV_TEAM;
   __shared__ fp_t lds[kTeams][2 * BGV_TEAM_COMPS];
   __shared__ fp_t part[BGV_FOLD_TEAMS][BGV_TEAM_COMPS];
-  __shared__ fp_t W[BGV_TEAM_COMPS], WA[BGV_TEAM_COMPS], WB[BGV_TEAM_COMPS], WP[8 * BGV_TEAM_COMPS];
+  __shared__ fp_t W[BGV_TEAM_COMPS];
   const int team = threadIdx.x / BGV_TEAM, c = threadIdx.x % BGV_TEAM;
   const bool fold = team < BGV_FOLD_TEAMS;  // teams past the fold's 16 multiply ones
   const int cc = c < BGV_TEAM_COMPS ? c : c - 4;
@@ -227,7 +218,7 @@ __device__ __forceinline__ void final_fold_body(const bgv_dgroup* __restrict__ g
     x = o.mul(x, y);
     if (ss) x = o.mul(x, in ? ss[kFp12 * idx + fi] : one_c);  // grid-uniform branch
   }
-  // the eight partial products as a tree: every team multiplies at every level (the barriers
+  // the teams' partial products as a tree: every team multiplies at every level (the barriers
   // inside o.mul), team t keeps parts 2t and 2t + 1 of the level
   BGV_UNROLL for (int w = BGV_FOLD_TEAMS; w > 1; w >>= 1) {
     if (fold && c < BGV_TEAM_COMPS) part[team][cc] = x;
@@ -237,59 +228,30 @@ __device__ __forceinline__ void final_fold_body(const bgv_dgroup* __restrict__ g
   }
   if (gpkp) x = o.mul(x, uni && team == 0 ? reinterpret_cast<const fp_t*>(gpkp + gi)[fi] : one_c);  // grid-uniform
   if (gprod && gi < ngroups && team == 0 && c < BGV_TEAM_COMPS) reinterpret_cast<fp_t*>(gprod + gi)[fi] = x;
-  // the final exponentiation on the whole block with the wide products (bgv_team_dev.h)
   if (team == 0 && c < BGV_TEAM_COMPS) W[cc] = x;
   __syncthreads();
-  if constexpr (ENGINE == 2) {
-    // residue arithmetic (bgv_rns.h): W in, u (and gu, the verdict bits) out; every branch
-    // below is uniform over the block (gu, gu1 over the grid, g.ref1 over the block)
-    __shared__ rns_smem RS;
-    rns_ops ro;
-    ro.init(&RS, threadIdx.x);
-    const uint32_t u = tm_final_exp_u(ro, ro.from_fp(W[ro.c]));
-    const int rfi = tm_fp_index(ro.c);
-    if (gu && gi < ngroups) {
-      const fp_t uf = ro.to_fp(u);
-      if (ro.i == 0) reinterpret_cast<fp_t*>(gu + gi)[rfi] = uf;
-    }
-    int32_t v = ro.is_fp6(u) ? 1 : 0;
-    if (gu1 && g.ref1) {  // see verdict_bits
-      const uint32_t ur = ro.from_fp(reinterpret_cast<const fp_t*>(gu1 + (g.ref1 - 1))[rfi]);
-      if (ro.is_fp6(ro.mul(ur, ro.conj(u)))) v |= 2;
-    }
-    if (gi < ngroups && threadIdx.x == 0) verdict[gi] = v;
-  } else {
-    const int wc = threadIdx.x % BGV_TEAM_COMPS, wq = threadIdx.x / BGV_TEAM_COMPS;
-    using OW = decltype(bgv_fold_ops_pick<ENGINE == 1>());
-    OW ow;
-    ow.A = WA;
-    ow.B = WB;
-    ow.P = WP;
-    ow.c = wc;
-    ow.q = wq;
-    if constexpr (ENGINE == 1) tm_sqr_rec8(wc, wq, &ow.rx, &ow.ry);
-    const fp_t xw = W[wc];
-    const int wfi = tm_fp_index(wc);
-    const fp_t u = tm_final_exp_u(ow, xw);
-    if (gu && gi < ngroups && wq == 0) reinterpret_cast<fp_t*>(gu + gi)[wfi] = u;
-    const int32_t v = verdict_bits(ow, u, g, gu1, wfi);
-    if (gi < ngroups && threadIdx.x == 0) verdict[gi] = v;
+  // the final exponentiation in residue arithmetic (bgv_rns.h) on the whole block: W in, u (and
+  // gu, the verdict bits) out; every branch below is uniform over the block (gu, gu1 over the
+  // grid, g.ref1 over the block)
+  __shared__ rns_smem RS;
+  rns_ops ro;
+  ro.init(&RS, threadIdx.x);
+  const uint32_t u = tm_final_exp_u(ro, ro.from_fp(W[ro.c]));
+  const int rfi = tm_fp_index(ro.c);
+  if (gu && gi < ngroups) {
+    const fp_t uf = ro.to_fp(u);
+    if (ro.i == 0) reinterpret_cast<fp_t*>(gu + gi)[rfi] = uf;
   }
+  int32_t v = ro.is_fp6(u) ? 1 : 0;
+  if (gu1 && g.ref1) {  // see verdict_bits
+    const uint32_t ur = ro.from_fp(reinterpret_cast<const fp_t*>(gu1 + (g.ref1 - 1))[rfi]);
+    if (ro.is_fp6(ro.mul(ur, ro.conj(u)))) v |= 2;
+  }
+  if (gi < ngroups && threadIdx.x == 0) verdict[gi] = v;
 }
 extern "C" {
-#define BGV_FOLD_ARGS                                                                                         \
-  const bgv_dgroup *__restrict__ groups, uint32_t ngroups, const fp12_t *__restrict__ f,                     \
-      const fp12_t *__restrict__ gpair, int32_t *__restrict__ verdict, fp12_t *__restrict__ gprod,          \
-      fp12_t *__restrict__ gu, const fp12_t *__restrict__ gu1, const fp12_t *__restrict__ fsig,                \
-      const fp12_t *__restrict__ gpkp
 __global__ void __launch_bounds__(BGV_FOLD_RNS_THREADS) k_final_fold(BGV_FOLD_ARGS) {
-  final_fold_body<2>(groups, ngroups, f, gpair, verdict, gprod, gu, gu1, fsig, gpkp);
-}
-__global__ void __launch_bounds__(BGV_FOLD_THREADS) k_final_fold_p8(BGV_FOLD_ARGS) {
-  final_fold_body<1>(groups, ngroups, f, gpair, verdict, gprod, gu, gu1, fsig, gpkp);
-}
-__global__ void __launch_bounds__(BGV_FOLD_THREADS) k_final_fold_sel(BGV_FOLD_ARGS) {
-  final_fold_body<0>(groups, ngroups, f, gpair, verdict, gprod, gu, gu1, fsig, gpkp);
+  final_fold_body(groups, ngroups, f, gpair, verdict, gprod, gu, gu1, fsig, gpkp);
 }
 
 // Products of runs of Fp12 values (cross-process partials): team t of the
@@ -375,37 +337,27 @@ hipError_t bgv_launch_groups(const bgv_dev_batch& b, const bgv_streams& s, bool 
     const hipError_t e = bgv_launch_gpairs(b, s.main);
     if (e != hipSuccess) return e;
   }
-  static const bool lean = [] {
-    const char* e = getenv("BGV_FOLD_LEAN");
-    return !(e && atoi(e) == 0);
-  }();
-  static const bool rns = [] {
-    const char* e = getenv("BGV_FOLD_RNS");
-    return !(e && atoi(e) == 0);
-  }();
   if (b.weighted && !b.gu) return hipErrorInvalidValue;
-  // A retry round of a uniform batch (b.uniform: tests inside uniform first-pass groups, whose
-  // slots have no pair f_i of their own) closes on k_final12, which multiplies the tests' pubkey-
-  // sum pairs (gpkp), whatever its size: its b.ngroups counts only the round's tests, so a batch
-  // just above the latency bound on its first pass can fall below it here (advisor r05), and
-  // k_final_fold would multiply the groups' unwritten f_i instead.
-  // A retry round of a uniform batch with at most BGV_RETRY_FOLD_MAX tests (env; 0: none)
-  // closes on k_final_fold whatever the batch's size: one block per test, its final
-  // exponentiation in residue arithmetic (~0.55 against ~2.8 ms for k_final12's teams) at ~6x
-  // the SIMD time per test.  Mainnet-shaped windows (uniform batches, their rate bound by the
-  // retry thread's round latency): 5.05-5.17 against 4.47-4.81 M sets/s; on the headline's
-  // non-uniform batches it cost 0.4 % (512 tests) to 30 % (every round), so those stay on
-  // k_final12 (profiles/r06/retry_fold/).
+  // Routing.  A non-uniform batch (first pass or retry round) within the latency bound closes on
+  // k_final_fold, a larger one on k_final12.  A uniform batch's first pass closes on k_final12.
+  // Its retry rounds (b.uniform: tests inside uniform first-pass groups, whose slots have no pair
+  // f_i of their own; both kernels multiply the tests' pubkey-sum pairs gpkp instead) are routed
+  // by the round's own test count, never by the latency bound: at most BGV_RETRY_FOLD_MAX tests
+  // (env; 0: none) close on k_final_fold, more on k_final12.  The fold
+  // takes one block per test, its final exponentiation in residue arithmetic (~0.55 against
+  // ~2.8 ms for k_final12's teams) at ~6x the SIMD time per test.  Mainnet-shaped windows (uniform
+  // batches, their rate bound by the retry thread's round latency): 5.05-5.17 against 4.47-4.81 M
+  // sets/s; on the headline's non-uniform batches it cost 0.4 % (512 tests) to 30 % (every round),
+  // so their retry rounds stay on k_final12 unless the round fits the latency bound
+  // (profiles/r06/retry_fold/).
   static const uint32_t retry_fold_max = [] {
     const char* e = getenv("BGV_RETRY_FOLD_MAX");
     return e ? (uint32_t)atoi(e) : (uint32_t)BGV_RETRY_FOLD_MAX;
   }();
   const bool small_retry = pairs && b.uniform && b.ngroups <= retry_fold_max;
   if ((!b.uniform && b.nslots + b.ngroups <= bgv_latency_max()) || small_retry)
-    hipLaunchKernelGGL(rns ? k_final_fold : (lean ? k_final_fold_p8 : k_final_fold_sel), dim3(b.ngroups),
-                       dim3(rns ? BGV_FOLD_RNS_THREADS : BGV_FOLD_THREADS), 0, s.main, b.groups,
-                       b.ngroups, b.f, b.gpair,
-                       b.verdict, b.gprod, b.gu, b.gu1,
+    hipLaunchKernelGGL(k_final_fold, dim3(b.ngroups), dim3(BGV_FOLD_RNS_THREADS), 0, s.main, b.groups, b.ngroups, b.f,
+                       b.gpair, b.verdict, b.gprod, b.gu, b.gu1,
                        !pairs && bgv_sig_pairs(b) ? static_cast<const fp12_t*>(b.fsig) : nullptr,
                        b.uniform ? static_cast<const fp12_t*>(b.gpkp) : nullptr);
   else

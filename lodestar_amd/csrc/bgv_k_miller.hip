@@ -4,9 +4,9 @@
 //   prod_i e(r_i pk_i, H(m_i)) * e(-G1, sum_i r_i sig_i) == 1
 //
 //   k_gsum     per device group (a team of 16 lanes): S_g = sum of the group's r_i sig_i
-//   k_miller   f_i = MillerLoop(r_i pk_i, H(m_i)), one pair per lane, and on extra lanes
-//              one per group g_g = MillerLoop(-G1, S_g)
-//   k_gpair    retry rounds: the parts' signature pairs alone
+//   k_lines + k_facc  (bgv_k_miller_bulk.hip) f_i = MillerLoop(r_i pk_i, H(m_i)), one pair per
+//              lane, and on extra lanes one per group g_g = MillerLoop(-G1, S_g)
+//   k_gpair    retry rounds: the parts' signature pairs alone, one per lane
 //   k_miller_team  the latency path for small calls: the same pairs, one per team of 16
 //              lanes (bgv_tmiller.h), ~10x lower latency per pair than one lane
 #include "bgv_device.h"
@@ -19,29 +19,12 @@ static __constant__ uint8_t kTmProg[TMP_TABLE_BYTES] = TMP_TABLE_INIT;
 
 extern "C" {
 
-// Lanes [0, nslots): f_i = MillerLoop(r pk, H(m)), 1 for slots that do not take part.
-// Lanes [nslots, nslots + ngroups): the group's signature pair MillerLoop(-G1, S_g) (1 for
-// an infinite S_g), so the group pairs run beside the set pairs instead of after them.
+// A group's signature pair MillerLoop(-G1, S_g) (1 for an infinite S_g).
 // -G1 in Jacobian form, in memory for miller_loop1m
 static __device__ const g1_jac kNegG1Jac = {{BGV_G1X}, {BGV_NEG_G1Y}, {BGV_ONE}};
 
 __device__ __forceinline__ fp12_t group_pair(const g2_jac* S) {
   return jac_is_inf(*S) ? fp12_one() : miller_loop1m(&kNegG1Jac, S);
-}
-
-__global__ void BGV_KATTR k_miller(const bgv_dslot* __restrict__ slots, uint32_t nslots,
-                                   const g1_jac* __restrict__ rpk, const g2_jac* __restrict__ h,
-                                   const int32_t* __restrict__ sig_status, const int32_t* __restrict__ pk_status,
-                                   fp12_t* __restrict__ f, uint32_t ngroups, const g2_jac* __restrict__ gsum,
-                                   fp12_t* __restrict__ gpair) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < nslots) {
-    fp12_t r = fp12_one();
-    if (slot_live(slots[s], sig_status[s], pk_status[s])) r = miller_loop1m(rpk + s, h + slots[s].hsrc);
-    f[s] = r;
-  } else if (s - nslots < ngroups) {
-    gpair[s - nslots] = group_pair(gsum + (s - nslots));
-  }
 }
 
 // retry rounds: the signature pairs of the round's parts alone
@@ -410,7 +393,7 @@ static void launch_miller_latency(const bgv_dev_batch& b, uint32_t nslots, uint3
                        static_cast<const g1_jac*>(nullptr), static_cast<fp12_t*>(nullptr));
 }
 
-// lanes of one k_miller round: one wave of 64 on each SIMD (MI355X: 256 CUs x 4 SIMDs)
+// lanes of one k_facc round: one wave of 64 on each SIMD (MI355X: 256 CUs x 4 SIMDs)
 static uint32_t miller_round_lanes() {
   static const uint32_t lanes = [] {
     int dev = 0, cus = 256;
@@ -420,16 +403,6 @@ static uint32_t miller_round_lanes() {
     return (uint32_t)cus * 4u * 64u;
   }();
   return lanes;
-}
-
-// BGV_MILLER_1PASS=1: the single-pass k_miller (one lane holds f, T and P) instead of
-// k_lines + k_facc, for A/B measurements; it needs no line records
-bool bgv_single_pass_miller() {
-  static const bool v = [] {
-    const char* e = getenv("BGV_MILLER_1PASS");
-    return e && atoi(e) > 0;
-  }();
-  return v;
 }
 
 hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s) {
@@ -457,14 +430,7 @@ hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s) {
                        b.rpk, b.h, b.sig_status, b.pk_status, b.f, b.ngroups, b.gsum, b.gpair,
                        static_cast<const bgv_dgroup*>(nullptr), static_cast<const uint32_t*>(nullptr), 0u,
                        static_cast<const g1_jac*>(nullptr), static_cast<fp12_t*>(nullptr));
-    if (bgv_single_pass_miller())
-      hipLaunchKernelGGL(k_miller, dim3(nblk(n, 64)), dim3(64), 0, s.main, b.slots, n, b.rpk, b.h, b.sig_status,
-                         b.pk_status, b.f, 0u, b.gsum, b.gpair);
-    else if (hipError_t e = bgv_launch_miller_bulk(b, 0u, s.main); e != hipSuccess)
-      return e;
-  } else if (bgv_single_pass_miller()) {
-    hipLaunchKernelGGL(k_miller, dim3(nblk(n + b.ngroups, 64)), dim3(64), 0, s.main, b.slots, n, b.rpk, b.h,
-                       b.sig_status, b.pk_status, b.f, b.ngroups, b.gsum, b.gpair);
+    if (hipError_t e = bgv_launch_miller_bulk(b, 0u, s.main); e != hipSuccess) return e;
   } else if (hipError_t e = bgv_launch_miller_bulk(b, b.ngroups, s.main); e != hipSuccess) {
     return e;
   }

@@ -1,52 +1,47 @@
 // The bulk Miller loops of a verify call (gfx950), in two phases and in a unit of its own so
-// that each phase gets its own register budget (BGV_WPE_LINES / BGV_WPE_FACC waves per SIMD).
+// that each phase gets its own register budget (k_lines BGV_WPE_LINES waves per SIMD, k_facc one).
 // The per-set pairs of blst's randomized batch equation (maybeBatch.ts:18-25 ->
 // verifyMultipleAggregateSignatures):  f_i = MillerLoop(r_i pk_i, H(m_i)), and one pair per
 // device group g_g = MillerLoop(-G1, S_g).
 //
 //   k_lines  one lane per twist point Q (each distinct signing root's H, each group's S_g):
 //            walks T over the loop and writes the 68 P-free line records (bls_pairing.h
-//            lz_pline_dbl / lz_pline_add) to HBM.  Live set: T and one step's temporaries.
+//            miller_lines_walk: lz_pline_dbl_p / lz_pline_add_p) to HBM.  Live set: T and one
+//            step's temporaries.
 //   k_facc   one lane per pair: f <- f^2 * line(P) over the records of its Q.  The records are
 //            staged through LDS: each step's record is read from LDS and the next one's DMA
 //            (global_load_lds_dwordx4, no VGPR destination) issued right after, so it lands
 //            during the line product and the next squaring; P's three constants also wait in
 //            LDS between the steps' scalings.  Live set: f and the step's temporaries.
 //
-// One loop of the single-pass k_miller kept f (168 u32), T (84) and P (42) live across every
-// out-of-line product: 2.7 KB of scratch per lane and 230x its algorithmic HBM bytes
-// (DESIGN.md section 2).  Split, each phase's live set is smaller.
+// One loop of the earlier single-pass kernel (miller_loop1m, one lane per pair) kept f (168 u32),
+// T (84) and P (42) live across every out-of-line product: 2.7 KB of scratch per lane and 230x
+// its algorithmic HBM bytes.  Split, each phase's live set is smaller.
 //
 // Records: quad q (words 4q..4q+3) of record k (step k of the loop) of pair p is the 16 bytes at
 // lines[((k * 21 + q) * cap + p) * 4] (cap = the buffer's pairs): a wave's 64 lanes write and
 // read 1 KB contiguously, one dwordx4 instruction per quad.
-// -DBGV_BULK_MILLER_INLINE inlines this unit's Montgomery products (bls_lazy.h
-// BGV_LAZY_INLINE_MUL).  An out-of-line product costs 2,850 SIMD cycles per wave at one wave per
+// This unit's Montgomery products are calls, not inlined (bls_lazy.h BGV_LAZY_INLINE_MUL would
+// inline them).  An out-of-line product costs 2,850 SIMD cycles per wave at one wave per
 // SIMD against 2,080 inlined in a tight loop (tools/ubench_prod.hip, profiles/r04/ubench_prod.jsonl),
 // but inlined here the loop bodies grow to ~52k instructions (~400 KB, past the 64 KB
 // instruction cache) and the Miller stage measured 11.6-11.7 ms against 10.8-10.9 ms with calls
-// (profiles/r04/inline_ab/): not the default.
-#ifdef BGV_BULK_MILLER_INLINE
-#define BGV_LAZY_INLINE_MUL 1
-#endif
+// (profiles/r04/inline_ab/).
 // (Hand-scheduled exact-clobber product subroutines measured equal at the kernel level,
 // profiles/r04/asm_ab: k_miller 10.69-10.76 vs 10.71-10.86 ms; kept in tools/experimental/.)
 // Fp2 products with deferred reduction (bls_wide.h); k_lines and k_facc run 64-thread blocks,
 // as the products' per-lane LDS operand slot requires
-#ifndef BGV_LZ2_CLASSIC
 #define BGV_LZ2_WIDE 1
 #define BGV_LZ2_WIDE_STRICT 1  // no silent fallback to the fully reduced product
-#endif
 #include "bgv_device.h"
 
 #ifndef BGV_WPE_LINES
 #define BGV_WPE_LINES 1
 #endif
-#ifndef BGV_WPE_FACC
-#define BGV_WPE_FACC 1
-#endif
 #define BGV_KATTR_LINES __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BGV_WPE_LINES, BGV_WPE_LINES)))
-#define BGV_KATTR_FACC __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BGV_WPE_FACC, BGV_WPE_FACC)))
+// k_facc at one wave per SIMD: at two, without room for the LDS staging, 17.9 against 9.5 ms
+// (profiles/r06/ab_twowave/)
+#define BGV_KATTR_FACC __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 
 static_assert(sizeof(lz_pline_d) == 4 * BGV_LINE_WORDS, "line record layout");
 static_assert(sizeof(lz_pline_a) == 4 * BGV_LINE_WORDS, "line record layout");
@@ -130,26 +125,6 @@ __global__ void BGV_KATTR_FACC k_facc(const bgv_dslot* __restrict__ slots, uint3
     *out = fp12_one();
     return;
   }
-#if BGV_WPE_FACC >= 2
-  // Two waves per SIMD (A/B: BGV_WPE_FACC=2): 8 waves per CU leave 20 KB of LDS each, so no
-  // staging -- the records are read straight into registers (the other wave hides the loads)
-  // and P's constants stay in registers; the LDS holds only the products' operand slot.
-  {
-    const uint32_t* base = lines + 4 * (size_t)lp;
-    const miller_p P0 = miller_p_make(*P);
-    *out = miller_facc_walk_staged([&](int k, uint32_t z, auto* r) {
-      const uint4* src = reinterpret_cast<const uint4*>(base + (size_t)(k + z) * BGV_LINE_QUADS * 4 * cap);
-      uint4* w = reinterpret_cast<uint4*>(r);
-      BGV_UNROLL for (int d = 0; d < BGV_LINE_QUADS; ++d) w[d] = src[(size_t)d * cap];
-    }, [&](int which, uint32_t z) {
-      const fp_t& c = which == 0 ? P0.xn : (which == 1 ? P0.yp : P0.zp3);
-      lzr v;
-      BGV_UNROLL for (int i = 0; i < NL; ++i) v.v[i] = c.v[i] + z;
-      return v;
-    });
-    return;
-  }
-#endif
   // this wave's LDS: the staged record [quad][lane] and P's constants [word][lane]
   __shared__ uint4 rec_lds[BGV_LINE_QUADS][64];
   __shared__ uint32_t p_lds[3 * NL][64];
@@ -186,7 +161,7 @@ __global__ void BGV_KATTR_FACC k_facc(const bgv_dslot* __restrict__ slots, uint3
 // line records a batch's bulk Miller launch writes: one per set pair's twist point (slot index
 // space) and one per group; 0 when the batch takes the latency path or has no slots
 uint32_t bgv_lines_pairs(const bgv_dev_batch& b) {
-  if (b.nslots == 0 || bgv_use_latency(b, b.nslots + b.ngroups) || bgv_single_pass_miller()) return 0;
+  if (b.nslots == 0 || bgv_use_latency(b, b.nslots + b.ngroups)) return 0;
   return b.nslots + b.ngroups;
 }
 size_t bgv_line_record_bytes() { return (size_t)BGV_MILLER_STEPS * BGV_LINE_WORDS * 4; }

@@ -100,7 +100,6 @@ hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s);
 // bulk path: k_lines + k_facc over the set pairs and the first ngroups group pairs
 hipError_t bgv_launch_miller_bulk(const bgv_dev_batch& b, uint32_t ngroups, hipStream_t st);
 uint32_t bgv_lines_pairs(const bgv_dev_batch& b);  // line records the batch needs (0: latency path)
-bool bgv_single_pass_miller();                     // BGV_MILLER_1PASS: k_miller instead (A/B)
 size_t bgv_line_record_bytes();                    // bytes of one pair's 68 records
 hipError_t bgv_launch_groups(const bgv_dev_batch& b, const bgv_streams& s, bool pairs);
 // bgv_launch_groups closes with k_final12 iff

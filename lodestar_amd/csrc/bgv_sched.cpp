@@ -363,8 +363,8 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   }
   const size_t ncom = ncom_team + ncom_wave, nlist = nuniq + ncom;  // the lists after the indices
   const bool bulk = nslots + ngroups > bgv_fold_pairs_max();
-  // uniform groups (BGV_GROUP_UNIFORM): bulk batches on the two-phase Miller stage
-  const bool uniform = uniform_enabled() && any_uniform && bulk && !bgv_single_pass_miller();
+  // uniform groups (BGV_GROUP_UNIFORM): bulk batches (the two-phase Miller stage)
+  const bool uniform = uniform_enabled() && any_uniform && bulk;
   HIPCHK(hipSetDevice(d.id));
   int rc;
   if ((rc = exec_reserve_slots(x, nslots)) || (rc = exec_reserve_groups(x, ngroups)) ||

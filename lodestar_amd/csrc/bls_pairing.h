@@ -264,8 +264,8 @@ BGV_HD fp12_t miller_loop1(const g1_jac& p, const g2_jac& q) { return miller_loo
 //            l3 = L3 Y_P, with (L0, L1, L3) below.  Lines depend on Q only, so a signing root
 //            shared by many sets is walked once (hash_to_G2 once per root, bgv_dslot.hsrc).
 //   k_facc   keeps only f and P: per step f <- f^2 * (L scaled by P).
-// The scaled lines are the same field elements as lz_miller_dbl_lines / miller_add_jq's, so
-// f is the same field element as miller_loop1m's (bit-identical after canonicalisation).
+// The scaled lines are those of miller_loop1m up to Fp2 factors (the walk below is projective),
+// so f has the same pairing value as miller_loop1m's.
 // Line record: 68 steps (the first doubling, then per bit 61..0 an addition where the next
 // bit of |x| is set and a doubling) x (L0, L1, L3) = 6 Fp = 84 u32 limbs.
 // ---------------------------------------------------------------------------
@@ -280,65 +280,19 @@ struct lz_pline_t {
   C L3;
 };
 
-// doubling step: L0 = 3 X^3 - 2 Y^2, L1 = 3 X^2 Z^2, L3 = Z3 Z^2 (E = 3A as in lz_miller_dbl_lines)
-BGV_MILLER_ATTR auto lz_pline_dbl(lz_tpt& t) {
-  const lz2r A = lz2_sqr(t.x);
-  const lz2r B = lz2_sqr(t.y);
-  const lz2r C = lz2_sqr(B);
-  const lz2r ZZ = lz2_sqr(t.z);
-  const auto D = lz2_norm(lz2_dbl(lz2_sub(lz2_sqr(lz2_norm(lz2_add(t.x, B))), lz2_add(A, C))));
-  const auto L0 = lz2_norm(lz2_sub(lz2_mulk<3>(lz2_mul(A, t.x)), lz2_dbl(B)));
-  const auto L1 = lz2_norm(lz2_mulk<3>(lz2_mul(A, ZZ)));
-  const auto X3 = lz2_sub(lz2_mulk<9>(lz2_sqr(A)), lz2_dbl(D));
-  const auto Y3 = lz2_sub(lz2_mulk<3>(lz2_mul(A, lz2_norm(lz2_sub(D, X3)))), lz2_mulk<8>(C));
-  const auto Z3 = lz2_sub(lz2_sqr(lz2_norm(lz2_add(t.y, t.z))), lz2_add(B, ZZ));
-  const auto L3 = lz2_norm(lz2_mul(lz2_wnorm(Z3), ZZ));
-  t.x = lz2_red(X3);
-  t.y = lz2_red(Y3);
-  t.z = lz2_red(Z3);
-  return lz_pline_t<std::decay_t<decltype(L0)>, std::decay_t<decltype(L1)>, std::decay_t<decltype(L3)>>{L0, L1, L3};
-}
-
-// addition step T + Q, Q = (X2 : Y2 : Z2) Jacobian (miller_add_jq without the P factors):
-// L0 = r X2 Z2 - Y2 Z3, L1 = r Z2^3, L3 = Z3 Z2^3
-BGV_MILLER_ATTR auto lz_pline_add(lz_tpt& t, const lz2r& qx, const lz2r& qy, const lz2r& qz) {
-  const lz2r zz = lz2_sqr(qz);
-  const auto zzz = lz2_norm(lz2_mul(zz, qz));
-  const auto xz = lz2_norm(lz2_mul(qx, qz));
-  const lz2r ZZ = lz2_sqr(t.z);
-  const auto U1 = lz2_mul(t.x, zz);
-  const auto U2 = lz2_mul(qx, ZZ);
-  const auto S1 = lz2_mul(t.y, zzz);
-  const auto S2 = lz2_mul(qy, lz2_mul(t.z, ZZ));
-  const auto H = lz2_norm(lz2_sub(U2, U1));
-  const lz2r HH = lz2_sqr(H);
-  const auto J = lz2_mulk<4>(lz2_mul(H, HH));
-  const lz2r r = lz2_red(lz2_dbl(lz2_sub(S2, S1)));
-  const auto V = lz2_mulk<4>(lz2_mul(U1, HH));
-  const auto X3 = lz2_norm(lz2_sub(lz2_sqr(r), lz2_add(J, lz2_dbl(V))));
-  const auto Y3 = lz2_sub(lz2_mul(r, lz2_norm(lz2_sub(V, X3))), lz2_dbl(lz2_mul(S1, lz2_norm(J))));
-  const auto Z3 = lz2_mul(lz2_wnorm(lz2_sub(lz2_sqr(lz2_norm(lz2_add(t.z, qz))), lz2_add(ZZ, zz))), H);
-  const auto L0 = lz2_norm(lz2_sub(lz2_mul(r, xz), lz2_mul(qy, Z3)));
-  const auto L1 = lz2_norm(lz2_mul(r, zzz));
-  const auto L3 = lz2_norm(lz2_mul(Z3, zzz));
-  t.x = lz2_red(X3);
-  t.y = lz2_red(Y3);
-  t.z = lz2_red(Z3);
-  return lz_pline_t<std::decay_t<decltype(L0)>, std::decay_t<decltype(L1)>, std::decay_t<decltype(L3)>>{L0, L1, L3};
-}
-
-// Round 6: the bulk walk (k_lines) in homogeneous projective coordinates, x = X/Z, y = Y/Z.
+// The bulk walk (k_lines) in homogeneous projective coordinates, x = X/Z, y = Y/Z.
 // Doubling (a = 0, b' = 4(1 + i); Costello-Lange-Naehrig, all coordinates times 4): B = Y^2,
 // C = Z^2, E = 3 b' C, F = 3E, H = (Y + Z)^2 - B - C = 2YZ,
 //   X3 = 2XY (B - F), Y3 = (B + F)^2 - 12 E^2, Z3 = 4 B H,
 // and the tangent scaled by 2YZ: H yP - 3X^2 xP + (B - E), i.e. L0 = B - E, L1 = 3X^2, L3 = H in
 // the records' convention (l = L0 - L1 xP + L3 yP, scaled by P as before): 3 products + 6
-// squarings against the Jacobian step's 4 + 7.  Addition T + Q (Q projective; add-1998-cmo-2):
+// squarings against the 4 + 7 of a Jacobian step (lz_miller_dbl_lines).  Addition T + Q (Q
+// projective; add-1998-cmo-2):
 // u = Y2 Z1 - Y1 Z2, v = X2 Z1 - X1 Z2, X3 = v A, Y3 = u (R - A) - v^3 Y1 Z2, Z3 = v^3 Z1 Z2
 // (R = v^2 X1 Z2, A = u^2 Z1 Z2 - v^3 - 2R), the chord through Q scaled by v Z2:
 // L0 = u X2 - v Y2, L1 = u Z2, L3 = v Z2.  Other representatives of the same lines (Fp2
-// factors the final exponentiation removes): the same pairing values as the Jacobian walk
-// (tests/test_pairing_golden.py, and on the device tests/test_gpu_pairing.py).
+// factors the final exponentiation removes): the same pairing values as miller_loop1m's
+// Jacobian steps (tests/test_pairing_golden.py, and on the device tests/test_gpu_pairing.py).
 BGV_MILLER_ATTR auto lz_pline_dbl_p(lz_tpt& t) {
   const lz2r B = lz2_sqr(t.y);
   const lz2r C = lz2_sqr(t.z);
@@ -387,13 +341,8 @@ BGV_HD lz_tpt lz_tpt_proj(const g2_jac& q) {
 }
 
 // the record types the two phases agree on
-#if defined(BGV_LINES_JACOBIAN)  // A/B: round 5's Jacobian walk
-typedef decltype(lz_pline_dbl(*(lz_tpt*)nullptr)) lz_pline_d;
-typedef decltype(lz_pline_add(*(lz_tpt*)nullptr, lz2r{}, lz2r{}, lz2r{})) lz_pline_a;
-#else
 typedef decltype(lz_pline_dbl_p(*(lz_tpt*)nullptr)) lz_pline_d;
 typedef decltype(lz_pline_add_p(*(lz_tpt*)nullptr, lz2r{}, lz2r{}, lz2r{})) lz_pline_a;
-#endif
 
 // the line of a record scaled by P (6 products), as an Fp12 factor's three coefficients
 template <class Lp>
@@ -459,18 +408,6 @@ BGV_HD bool miller_add_at(int i) { return (BGV_X_ABS >> (i + 1)) & 1; }
 // the loads), so the 63 doublings keep only T and their temporaries live.
 template <class Emit>
 BGV_HD void miller_lines_walk(const g2_jac* qm, Emit emit) {
-#if defined(BGV_LINES_JACOBIAN)
-  lz_tpt t = {lz2_in(qm[0].x), lz2_in(qm[0].y), lz2_in(qm[0].z)};
-  int k = 0;
-  emit(k++, lz_pline_dbl(t));
-  BGV_NO_UNROLL for (int i = 61; i >= 0; --i) {
-    if (miller_add_at(i)) {
-      const g2_jac& q = qm[bgv_opaque0()];
-      emit(k++, lz_pline_add(t, lz2_in(q.x), lz2_in(q.y), lz2_in(q.z)));
-    }
-    emit(k++, lz_pline_dbl(t));
-  }
-#else
   lz_tpt t = lz_tpt_proj(qm[0]);
   int k = 0;
   emit(k++, lz_pline_dbl_p(t));
@@ -481,7 +418,6 @@ BGV_HD void miller_lines_walk(const g2_jac* qm, Emit emit) {
     }
     emit(k++, lz_pline_dbl_p(t));
   }
-#endif
 }
 
 // k_facc's walk with the records and P's constants in LDS: load(k, rec) fills record k,

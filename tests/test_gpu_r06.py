@@ -3,8 +3,11 @@
 Retry rounds of uniform groups just above the latency bound (advisor r05, high): a bulk call
 whose first pass is uniform (nslots + ngroups > BGV_LATENCY_MAX, one Miller loop per group over
 its pubkey sum) runs retry rounds with only a few test groups, so nslots + nrg can fall below
-the bound.  The closing must still be k_final12 (it multiplies the tests' pubkey-sum pairs);
-k_final_fold would multiply the uniform groups' unwritten per-slot f_i and reject valid jobs.
+the bound.  Such a round is routed by its own test count, never by the latency bound: at most
+BGV_RETRY_FOLD_MAX (512) tests close on k_final_fold, more on k_final12, and either kernel
+multiplies the tests' pubkey-sum pairs (gpkp) -- the uniform groups' per-slot f_i are unwritten,
+and a closing that multiplied them would reject valid jobs.  The rounds here are small, so they
+close on k_final_fold (tests/test_gpu_uniform_retry_closings.py pins both closings).
 Every verdict must equal the job verified alone (chain/bls/multithread/worker.ts:76-98).
 """
 import hashlib
