@@ -239,6 +239,7 @@ struct BatchState {
   std::vector<uint32_t> call_gb;  // each call's first group in the merged batch
   bool want_gu = false;           // the first pass's u values are in x.d_gu1 (pattern tests)
   bool uniform = false;           // the first pass ran uniform groups (their slots have no own pair f_i)
+  bool bulk = false;              // the first pass took the bulk path: retry rounds feed their teams line records
   bool prof = false;
 };
 // A super-batch whose first pass is done and whose retry rounds wait for the retry thread.
@@ -395,6 +396,7 @@ void exec_destroy(Exec* x);
 int exec_reserve_slots(Exec& x, uint32_t slots);
 int exec_reserve_groups(Exec& x, uint32_t groups);
 int exec_reserve_lines(Exec& x, bgv_dev_batch& b);
+int exec_reserve_line_pairs(Exec& x, bgv_dev_batch& b, uint32_t need);  // a retry round's team pairs
 bgv_dev_batch make_batch(Device& d, Exec& x, uint32_t nslots, uint32_t ngroups);
 int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code,
                   const bgv_pkbits* pkbits = nullptr, Call* call = nullptr);

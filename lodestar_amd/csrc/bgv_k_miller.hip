@@ -6,9 +6,11 @@
 //   k_gsum     per device group (a team of 16 lanes): S_g = sum of the group's r_i sig_i
 //   k_lines + k_facc  (bgv_k_miller_bulk.hip) f_i = MillerLoop(r_i pk_i, H(m_i)), one pair per
 //              lane, and on extra lanes one per group g_g = MillerLoop(-G1, S_g)
-//   k_gpair    retry rounds: the parts' signature pairs alone, one per lane
 //   k_miller_team  the latency path for small calls: the same pairs, one per team of 16
 //              lanes (bgv_tmiller.h), ~10x lower latency per pair than one lane
+//   k_miller_team_fed  retry rounds of bulk batches without uniform groups: the parts'
+//              signature pairs, the team keeping only the Fp12 accumulator and reading the
+//              lines a k_lines_team lane (bgv_k_miller_bulk.hip) walked for it
 #include "bgv_device.h"
 #include "bgv_team_dev.h"
 #include "bgv_tmiller.h"
@@ -16,24 +18,6 @@
 
 static __constant__ uint8_t kTmProg[TMP_TABLE_BYTES] = TMP_TABLE_INIT;
 
-
-extern "C" {
-
-// A group's signature pair MillerLoop(-G1, S_g) (1 for an infinite S_g).
-// -G1 in Jacobian form, in memory for miller_loop1m
-static __device__ const g1_jac kNegG1Jac = {{BGV_G1X}, {BGV_NEG_G1Y}, {BGV_ONE}};
-
-__device__ __forceinline__ fp12_t group_pair(const g2_jac* S) {
-  return jac_is_inf(*S) ? fp12_one() : miller_loop1m(&kNegG1Jac, S);
-}
-
-// retry rounds: the signature pairs of the round's parts alone
-__global__ void BGV_KATTR k_gpair(uint32_t ngroups, const g2_jac* __restrict__ gsum, fp12_t* __restrict__ gpair) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < ngroups) gpair[g] = group_pair(gsum + g);
-}
-
-}  // extern "C"
 // A lane's share of sum_k (k + 1) P_k over slots k = c + 16 t (t = 0..3) of its team:
 // (c + 1) A + 16 B with A = sum_t P_t and B = sum_t t P_t = S1 + S2 + S3, the suffix sums
 // S_t = sum_{t' >= t} P_t' taken from t = 3 down (no array of points: the kernel's stack frame
@@ -254,6 +238,68 @@ __global__ void __launch_bounds__(64) k_miller_team(BGV_MTEAM_ARGS) {
                    gpkp);
 }
 
+// The group pairs e(-G1, S_g) of k_miller_team with the twist-point walk taken out: a
+// k_lines_team lane has walked S_g and left its 68 lines, scaled by -G1, at
+// lines + miller_fed_rec_word(g, k) (bgv_k_miller_bulk.hip).  The team only keeps the Fp12
+// accumulator: per step a squaring and a line product, no program table, no point slots.
+// Lane c of the team fetches quad c of the next record (lanes 0..4 also quad 16 + c) right
+// after the barrier that publishes the current one, so the load lands during the line product
+// and the next squaring; the record reaches the team's LDS with the accumulator, under the
+// line product's own first barrier.  The value is another representative than
+// k_miller_team's (projective lines: Fp2 factors the final exponentiation removes), the same
+// as k_facc's.  Teams past the end and pairs that take no part compute on zeros and store 1 or
+// nothing, so every lane reaches every barrier.
+__global__ void __launch_bounds__(64) k_miller_team_fed(uint32_t ngroups, const g2_jac* __restrict__ gsum,
+                                                        fp12_t* __restrict__ gpair,
+                                                        const uint32_t* __restrict__ lines) {
+  __shared__ fp_t lds[BGV_FINAL_TEAMS][2 * BGV_TEAM_COMPS];
+  __shared__ uint4 rec[BGV_FINAL_TEAMS][BGV_LINE_QUADS];
+  static_assert(BGV_LINE_QUADS > BGV_TEAM && BGV_LINE_QUADS <= 2 * BGV_TEAM, "two quads per lane at most");
+  const int team = threadIdx.x / BGV_TEAM, c = threadIdx.x % BGV_TEAM;
+  const int cc = c < BGV_TEAM_COMPS ? c : c - 4;
+  const uint32_t total = ngroups;
+  const uint32_t u = blockIdx.x * BGV_FINAL_TEAMS + team;
+  const uint32_t uu = u < total ? u : total - 1;
+  const bool live = !jac_is_inf(gsum[uu]);
+  fp12_t* dst = gpair + uu;
+  fp_t* A = lds[team];
+  uint4* R = rec[team];
+  const bool second = c < BGV_LINE_QUADS - BGV_TEAM;
+  const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+  uint4 n0 = zero4, n1 = zero4;  // the lane's quads of the record fetched ahead
+  auto fetch = [&](int k) {  // a pair that takes no part has no records: zeros
+    if (!live) return;
+    const uint4* src = reinterpret_cast<const uint4*>(lines + miller_fed_rec_word(uu, k));
+    n0 = src[c];
+    if (second) n1 = src[BGV_TEAM + c];
+  };
+  int k = 0;
+  // f * (record k's line), or the line itself for the first step; fetches record k + 1
+  auto feed = [&](const fp_t& x, bool first) {
+    if (c < BGV_TEAM_COMPS) A[c] = x;
+    R[c] = n0;
+    if (second) R[BGV_TEAM + c] = n1;
+    __syncthreads();
+    if (++k < BGV_MILLER_STEPS) fetch(k);
+    fp2_t l0, l1, l3;
+    lz_sline_fp2(reinterpret_cast<const uint32_t*>(R), &l0, &l1, &l3);
+    const fp_t r = first ? tm_line_lane(cc, l0, l1, l3) : tm_mul_line_lane(cc, A, l0, l1, l3);
+    __syncthreads();
+    return r;
+  };
+  tm_dev_ops o{A, A + BGV_TEAM_COMPS, c, cc};
+  fetch(0);
+  fp_t x = feed(fp_zero(), true);
+  BGV_NO_UNROLL for (int i = 61; i >= 0; --i) {
+    if (tmp_add_at(i)) x = feed(x, false);
+    x = o.sqr(x);
+    x = feed(x, false);
+  }
+  x = o.conj(x);
+  if (u < total && c < BGV_TEAM_COMPS)
+    reinterpret_cast<fp_t*>(dst)[tm_fp_index(cc)] = live ? x : (cc == 0 ? fp_one() : fp_zero());
+}
+
 // The same pairs with one pair per block for the smallest calls, on two waves that run the
 // loop's two chains side by side: wave 0 the twist-point rounds of k_miller_team as
 // four-part instructions (bgv_tround_dev.h), wave 1 the Fp12 accumulator with the wide
@@ -405,6 +451,15 @@ static uint32_t miller_round_lanes() {
   return lanes;
 }
 
+// the signature pairs of a retry round whose line records are reserved: the scaled walk, then
+// the fed teams
+static hipError_t launch_miller_fed(const bgv_dev_batch& b, hipStream_t st) {
+  if (hipError_t e = bgv_launch_lines_team(b, st); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_miller_team_fed, dim3(nblk(b.ngroups, BGV_FINAL_TEAMS)), dim3(64), 0, st, b.ngroups, b.gsum,
+                     b.gpair, static_cast<const uint32_t*>(b.lines));
+  return hipGetLastError();
+}
+
 hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s) {
   const uint32_t n = b.nslots;
   if (n == 0) return hipSuccess;
@@ -425,7 +480,8 @@ hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s) {
              (n + b.ngroups + R - 1) / R > (n + R - 1) / R && !b.uniform) {
     // the group pairs on extra k_facc lanes would open one more round of one wave per SIMD
     // (131,072 sets + 2,048 groups: 3 rounds instead of 2); run them on teams instead.  Not
-    // with uniform groups: their slot lanes exit at once, so no round is full anyway
+    // with uniform groups: their slot lanes exit at once, so no round is full anyway.  (Fed teams
+    // measured slower here: their walk is 2 ms of one lane per pair ahead of the set pairs)
     hipLaunchKernelGGL(k_miller_team, dim3(nblk(b.ngroups, BGV_FINAL_TEAMS)), dim3(64), 0, s.main, b.slots, 0u,
                        b.rpk, b.h, b.sig_status, b.pk_status, b.f, b.ngroups, b.gsum, b.gpair,
                        static_cast<const bgv_dgroup*>(nullptr), static_cast<const uint32_t*>(nullptr), 0u,
@@ -446,6 +502,9 @@ hipError_t bgv_launch_sets(const bgv_dev_batch& b, const bgv_streams& s) {
 // retry rounds over parts of failed groups: the parts' signature sums and pairs; with uniform
 // groups (b.uniform) also the pubkey sums and pubkey-sum pairs of the tests flagged
 // BGV_GROUP_UNIFORM (their slots have no own pair: bgv_retry_plan.h build_parts)
+#ifndef BGV_RETRY_WIDE_MAX
+#define BGV_RETRY_WIDE_MAX 1024
+#endif
 hipError_t bgv_launch_gpairs(const bgv_dev_batch& b, hipStream_t st) {
   if (b.ngroups == 0) return hipSuccess;
   hipLaunchKernelGGL(k_gsum, dim3(nblk(b.ngroups, BGV_FINAL_TEAMS)), dim3(64), 0, st, b.groups, b.ngroups, b.slots,
@@ -455,13 +514,24 @@ hipError_t bgv_launch_gpairs(const bgv_dev_batch& b, hipStream_t st) {
     hipLaunchKernelGGL(k_gsum_w, dim3(nblk(b.ngroups, BGV_FINAL_TEAMS)), dim3(64), 0, st, b.groups, b.ngroups,
                        b.slots, b.rsig, b.sig_status, b.pk_status, b.gsum, static_cast<const g1_jac*>(b.rpk),
                        static_cast<g1_jac*>(b.gpk));
+  // Without uniform groups, after a bulk first pass (the host reserved line records,
+  // retry_launch), the round's signature pairs run on fed teams.  Rounds of at most
+  // BGV_RETRY_WIDE_MAX tests (env, read once; 0: none, every such round is fed) keep
+  // k_miller_wide, two waves per pair: fed, the headline read 2.60 against 2.69-2.71 M sets/s.
+  // Rounds with uniform groups keep the walking teams: they are bound by the round's latency,
+  // and the walk's one lane per pair in front of the teams cost the mainnet-shaped leg 18 %
+  // (profiles/team_fed/).
+  static const uint32_t retry_wide_max = [] {
+    const char* e = getenv("BGV_RETRY_WIDE_MAX");
+    return e ? (uint32_t)atoi(e) : (uint32_t)BGV_RETRY_WIDE_MAX;
+  }();
   if (b.uniform)
     hipLaunchKernelGGL(k_miller_team, dim3(nblk(b.ngroups + b.npk, BGV_FINAL_TEAMS)), dim3(64), 0, st, b.slots, 0u,
                        b.rpk, b.h, b.sig_status, b.pk_status, b.f, b.ngroups, b.gsum, b.gpair, b.groups, b.upk, b.npk,
                        static_cast<const g1_jac*>(b.gpk), b.gpkp);
-  else if (b.ngroups <= bgv_latency_max())
+  else if (b.lines && !(b.ngroups <= retry_wide_max && b.ngroups <= BGV_MILLER_WIDE_MAX))
+    return launch_miller_fed(b, st);
+  else  // small rounds (k_miller_wide), and rounds after a latency first pass, which left no records
     launch_miller_latency(b, 0u, b.ngroups, st);
-  else
-    hipLaunchKernelGGL(k_gpair, dim3(nblk(b.ngroups, 64)), dim3(64), 0, st, b.ngroups, b.gsum, b.gpair);
   return hipGetLastError();
 }

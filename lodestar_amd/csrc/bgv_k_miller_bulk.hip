@@ -45,6 +45,7 @@
 
 static_assert(sizeof(lz_pline_d) == 4 * BGV_LINE_WORDS, "line record layout");
 static_assert(sizeof(lz_pline_a) == 4 * BGV_LINE_WORDS, "line record layout");
+static_assert(sizeof(lz_sline) == 4 * BGV_LINE_WORDS, "line record layout");
 
 static __device__ const g1_jac kNegG1JacB = {{BGV_G1X}, {BGV_NEG_G1Y}, {BGV_ONE}};
 
@@ -76,6 +77,26 @@ __global__ void BGV_KATTR_LINES k_lines(const bgv_dslot* __restrict__ slots, uin
     const uint4* w = reinterpret_cast<const uint4*>(&rec);
     uint4* dst = reinterpret_cast<uint4*>(base + (size_t)k * BGV_LINE_QUADS * 4 * cap);
     BGV_UNROLL for (int d = 0; d < BGV_LINE_QUADS; ++d) dst[(size_t)d * cap] = w[d];
+  });
+}
+
+// The walk of a retry round's signature pairs e(-G1, S_g) (k_miller_team_fed's): one lane per
+// group, the records scaled by -G1 (Z_P = 1: four scaling products per step) and pair-major
+// (bls_pairing.h lz_sline, miller_fed_rec_word).  An infinite S_g writes nothing (the team
+// stores 1 there).
+__global__ void BGV_KATTR_LINES k_lines_team(uint32_t ngroups, const g2_jac* __restrict__ gsum,
+                                             uint32_t* __restrict__ lines, uint32_t cap) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= ngroups || p >= cap) return;
+  const g2_jac* q = gsum + p;
+  if (jac_is_inf(*q)) return;
+  const miller_p P0 = miller_p_make(kNegG1JacB);
+  const lz_mp Pm = {lz_in(P0.xn), lz_in(P0.yp), lz_in(P0.zp3)};
+  miller_lines_walk(q, [&](int k, const auto& rec) {
+    const lz_sline s = lz_pline_scaled(rec, Pm, true);
+    const uint4* w = reinterpret_cast<const uint4*>(&s);
+    uint4* dst = reinterpret_cast<uint4*>(lines + miller_fed_rec_word(p, k));
+    BGV_UNROLL for (int d = 0; d < BGV_LINE_QUADS; ++d) dst[d] = w[d];
   });
 }
 
@@ -165,6 +186,14 @@ uint32_t bgv_lines_pairs(const bgv_dev_batch& b) {
   return b.nslots + b.ngroups;
 }
 size_t bgv_line_record_bytes() { return (size_t)BGV_MILLER_STEPS * BGV_LINE_WORDS * 4; }
+
+// the scaled records of a retry round's ngroups signature pairs (a small launch of its own)
+hipError_t bgv_launch_lines_team(const bgv_dev_batch& b, hipStream_t st) {
+  if (!b.lines || b.lines_cap < b.ngroups) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_lines_team, dim3(nblk(b.ngroups, 64)), dim3(64), 0, st, b.ngroups, b.gsum, b.lines,
+                     b.lines_cap);
+  return hipGetLastError();
+}
 
 // the set pairs [0, nslots), the group pairs [nslots, nslots + ngroups) and, with uniform
 // groups (b.uniform), their pubkey-sum pairs of a bulk batch; ngroups = 0 when the group pairs

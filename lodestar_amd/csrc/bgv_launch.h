@@ -99,13 +99,16 @@ hipError_t bgv_launch_prep_wave(const bgv_dev_batch& b, hipStream_t st);  // bgv
 hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s);
 // bulk path: k_lines + k_facc over the set pairs and the first ngroups group pairs
 hipError_t bgv_launch_miller_bulk(const bgv_dev_batch& b, uint32_t ngroups, hipStream_t st);
+// the scaled line records of a retry round's ngroups signature pairs for k_miller_team_fed,
+// pair-major in b.lines
+hipError_t bgv_launch_lines_team(const bgv_dev_batch& b, hipStream_t st);
 uint32_t bgv_lines_pairs(const bgv_dev_batch& b);  // line records the batch needs (0: latency path)
 size_t bgv_line_record_bytes();                    // bytes of one pair's 68 records
 hipError_t bgv_launch_groups(const bgv_dev_batch& b, const bgv_streams& s, bool pairs);
 // bgv_launch_groups closes with k_final12 iff
 // nslots + ngroups exceeds this (else k_final_fold)
 uint32_t bgv_fold_pairs_max();
-hipError_t bgv_launch_gpairs(const bgv_dev_batch& b, hipStream_t st);  // retry parts: k_gsum + k_gpair
+hipError_t bgv_launch_gpairs(const bgv_dev_batch& b, hipStream_t st);  // retry parts: sums, then pairs
 size_t bgv_slot_bytes();
 size_t bgv_slot_mem_bytes(uint32_t cap_slots);  // the per-slot arrays of an Exec of cap_slots slots
 size_t bgv_group_bytes();

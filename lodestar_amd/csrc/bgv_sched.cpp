@@ -97,8 +97,8 @@ static void exec_trim_lines(Exec& x, size_t max_slots) {
   x.d_lines = nullptr;
   x.lines_cap = 0;
 }
-int exec_reserve_lines(Exec& x, bgv_dev_batch& b) {
-  const uint32_t need = bgv_lines_pairs(b);
+int exec_reserve_lines(Exec& x, bgv_dev_batch& b) { return exec_reserve_line_pairs(x, b, bgv_lines_pairs(b)); }
+int exec_reserve_line_pairs(Exec& x, bgv_dev_batch& b, uint32_t need) {
   if (need > x.lines_cap) {
     const uint32_t cap = (need + 16383u) & ~16383u;
     if (x.d_lines) (void)hipFree(x.d_lines);
@@ -445,6 +445,7 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   b.max_npk = max_npk;
   b.uniform = uniform;
   bs.uniform = uniform;
+  bs.bulk = bgv_lines_pairs(b) != 0;
   b.uniq = x.d_idx + nidx;
   b.nuniq = (uint32_t)nuniq;
   b.com = x.d_idx + nidx + nuniq;
@@ -596,6 +597,9 @@ static int retry_launch(Device& d, RetryRun& r, bool* more) {
   bool pattern = false;
   for (Call* call : calls) pattern = pattern || !call->punits.empty();
   if (pattern) b.gu1 = x.d_gu1;
+  // after a bulk first pass without uniform groups the round's signature pairs read line records
+  // (bgv_launch_gpairs); the first pass's records are dead, and this thread holds the Exec
+  if (bs.bulk && !b.uniform && (rc = exec_reserve_line_pairs(x, b, nrg))) return rc;
   r.t_build = ms_since(th);
   bgv_streams SC{x.close, bs.prof ? x.kev : nullptr};
   HIPCHK(hipEventRecord(x.ev0, x.close));

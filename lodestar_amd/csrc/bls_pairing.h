@@ -420,6 +420,39 @@ BGV_HD void miller_lines_walk(const g2_jac* qm, Emit emit) {
   }
 }
 
+// Team pairs split the same way (retry rounds' signature pairs e(-G1, S_g), bgv_launch_gpairs):
+// one lane walks the pair's Q (k_lines_team) and writes each step's line ALREADY scaled by the
+// pair's P, l0 = L0 Z_P^3, l1 = L1 (-X_P Z_P), l3 = L3 Y_P (lz_pline_scale), fully reduced; the
+// team (k_miller_team_fed) then only squares f and multiplies it by the lines it reads.  A
+// scaled record is 3 Fp2 = BGV_LINE_WORDS words like a P-free one, and the 68 records of one
+// pair are contiguous (a team reads whole records): record k of pair p starts at word
+// miller_fed_rec_word(p, k) of the same buffer the P-free records use (cap pairs hold cap
+// pairs' records in either layout).
+struct lz_sline {
+  lz2r l0, l1, l3;
+};
+BGV_HD size_t miller_fed_rec_word(uint32_t pair, int k) {
+  return ((size_t)pair * BGV_MILLER_STEPS + (size_t)k) * BGV_LINE_WORDS;
+}
+// unit_z: Z_P = 1 (the constant -G1 of a signature pair), so l0 = L0 without a product
+template <class Lp>
+BGV_HD lz_sline lz_pline_scaled(const Lp& L, const lz_mp& P, bool unit_z) {
+  lz_sline r;
+  r.l0 = unit_z ? lz2_red(L.L0) : lz2_mul_fp(L.L0, P.zp3);
+  r.l1 = lz2_mul_fp(L.L1, P.xn);
+  r.l3 = lz2_mul_fp(L.L3, P.yp);
+  return r;
+}
+// the line of a scaled record as the team operations take it
+BGV_HD void lz_sline_fp2(const uint32_t* w, fp2_t* l0, fp2_t* l1, fp2_t* l3) {
+  fp_t v[6];
+  BGV_UNROLL for (int j = 0; j < 6; ++j)
+    BGV_UNROLL for (int i = 0; i < NL; ++i) v[j].v[i] = w[j * NL + i];
+  *l0 = fp2_t{v[0], v[1]};
+  *l1 = fp2_t{v[2], v[3]};
+  *l3 = fp2_t{v[4], v[5]};
+}
+
 // k_facc's walk with the records and P's constants in LDS: load(k, rec) fills record k,
 // pget(j) returns P's constant j (0 xn = -X Z, 1 yp = Y, 2 zp3 = Z^3).  The record of a
 // doubling is read after f^2 (lz12_after), when only f^2 is live.
