@@ -14,6 +14,7 @@ import pytest
 from oracle import bls12381 as o
 from tests import curvesim as cs
 from tests import hostsim as hs
+from tests.randomizer_edges import EDGE_WORDS
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 WORDS = [0, 1, 7, 8, 9, 0x88888888, 0x99999999, 0x77777777, 0x80000000, 0xFFFFFFFF]
@@ -31,6 +32,7 @@ def scalars():
     ks += [0xFFFFFFFFFFFFFFFF, (0x99999999 << 32) | 0x77777777, (1 << 32) | 0xFFFFFFFF]
     rnd = random.Random(0x16)
     ks += [rnd.getrandbits(64) for _ in range(64)]
+    ks += EDGE_WORDS  # the list the device routes are run over (tests/test_gpu_randomizer_edges.py)
     return sorted(set(ks))
 
 
@@ -99,6 +101,26 @@ def test_hash_to_g2_goldens(L):
         msg = bytes.fromhex(c["msg"])
         assert L.cs_hash_to_g2(out, msg, len(msg)) == 1
         assert o.g2_serialize(hs.b_g2(out.raw)) == bytes.fromhex(c["uncompressed"]), c["msg"]
+
+
+# Message lengths that put the hashed stream Z_pad(64) | msg | 3 bytes | DST'(44) of len + 111 bytes
+# on and around a SHA-256 block boundary: len + 111 = 55, 56, 63, 0, 1 (mod 64), the same one
+# block further (72, 73), and one unaligned long message.  The golden lengths (0, 3, 32, 100, 255)
+# reach none of them.
+PAD_EDGE_LENGTHS = [8, 9, 16, 17, 18, 72, 73, 137]
+
+
+def pad_edge_messages():
+    """One message per length, every byte depending on its position and on the length."""
+    return [bytes((37 * i + 11 * n + 1) & 0xFF for i in range(n)) for n in PAD_EDGE_LENGTHS]
+
+
+def test_hash_to_g2_padding_boundaries(L):
+    assert sorted({(n + 111) % 64 for n in PAD_EDGE_LENGTHS[:5]}) == [0, 1, 55, 56, 63]
+    out = hs.buf(192)
+    for msg in pad_edge_messages():
+        assert L.cs_hash_to_g2(out, msg, len(msg)) == 1
+        assert o.g2_serialize(hs.b_g2(out.raw)) == o.g2_serialize(o.hash_to_g2(msg)), len(msg)
 
 
 def test_standalone_sanitizer_run():

@@ -56,6 +56,19 @@ def test_hash_to_g2(ctx):
         assert got.hex() == c["uncompressed"], c["msg"]
 
 
+def test_hash_to_g2_padding_boundaries(ctx):
+    """Message lengths that put the device's hashed stream (bls_hash.h sha256_virtual: len + 111
+    bytes) on and around a SHA-256 block boundary, against the oracle, bit for bit."""
+    from oracle import bls12381 as o  # checker only
+    from tests.test_curve_recode import PAD_EDGE_LENGTHS, pad_edge_messages
+    msgs = pad_edge_messages()
+    assert [len(m) for m in msgs] == PAD_EDGE_LENGTHS == [8, 9, 16, 17, 18, 72, 73, 137]
+    outs = ctx.hash_to_g2(msgs)
+    assert len(outs) == len(msgs)
+    for msg, got in zip(msgs, outs):
+        assert got == o.g2_serialize(o.hash_to_g2(msg)), len(msg)
+
+
 def test_keygen_matches_interop_pubkeys(ctx):
     keys = load("keys.json")
     sks = b"".join(bytes.fromhex(s) for s in keys["sk"])

@@ -366,6 +366,28 @@ def test_team_g2_schedules(L):
             L.hs_set_wide_rounds(0)
 
 
+@pytest.mark.parametrize("wide", [1, 0], ids=["four-part", "plain"])
+def test_team_schedules_edge_words(L, wide):
+    """Every word of tests/randomizer_edges.py through the host emulation of the latency path's
+    r * pk (bgv_tg1.h, k_prep_wide's route) and r * sig (bgv_tcurve.h tc_mul_glv, k_prep_wide's
+    four-part rounds and k_prep_team's plain ones) against jac_mul_glv: the words the device
+    routes are run over in tests/test_gpu_randomizer_edges.py, so that a failure there with this
+    case green is in the device compile and not in the schedule."""
+    import ctypes
+    from tests.randomizer_edges import EDGE_WORDS
+    p = hs.g1_b(o.g1_mul(o.G1, 0x5EED0E5))
+    msg = hashlib.sha256(b"edge-words").digest()
+    L.hs_set_wide_rounds(wide)
+    try:
+        for k in EDGE_WORDS:
+            assert L.hs_tg1_check(p, ctypes.c_uint64(k)) == 1, (wide, hex(k))
+            bad = ctypes.c_int(7)
+            assert L.hs_tcurve_check(msg, ctypes.c_uint64(k), ctypes.byref(bad)) == 1, (wide, hex(k))
+            assert bad.value == 0, (wide, hex(k))
+    finally:
+        L.hs_set_wide_rounds(0)
+
+
 def test_team_mul_line(L):
     """Coefficient-parallel product with a sparse line equals the tower formula."""
     for _ in range(4):
