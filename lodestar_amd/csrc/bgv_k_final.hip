@@ -5,6 +5,42 @@
 
 #include "bgv_team_dev.h"
 #include "bgv_rns.h"
+#include "bgv_wfp.h"
+
+// 1 / nrm[team] (nrm: the block's NT nonzero norms in LDS) from ONE Fp inversion per block:
+// Montgomery's trick, every lane forming the same running products, and the inversion of their
+// total on the whole wave (bgv_wfp.h wfp_pow_fixed: every lane holds the same value, the control
+// flow is uniform).  The block is one wavefront; every lane of it calls this.
+template <int NT>
+__device__ __forceinline__ fp_t tm_block_inv(const fp_t* nrm, int team) {
+  fp_t out[NT];
+  tm_batch_inv_core<NT>(nrm, out, [](const fp_t& a) { return wfp_pow_fixed<BGV_POW_INV>(a); });
+  fp_t r = out[0];
+  BGV_UNROLL for (int i = 1; i < NT; ++i) r = fp_select(team == i, r, out[i]);
+  return r;
+}
+
+// The closing teams' final exponentiation (bls_team.h tm_easy_norm .. tm_final_exp_cyc) of x, with
+// the block's NT teams sharing the inversion; team >= NT (k_final12's idle lanes) and teams
+// without a group (own = false) take part in it with n = 1.  *zero: x has norm zero (it is not
+// invertible; its entry is replaced by 1 so the other teams' inverses stand, and the caller
+// clears the group's verdict bits).  Returns what gu holds: a representative u whose pairing
+// value is conj(u) / u, as tm_final_exp_u's.  U = x^(3 (p^12 - 1) / r) is unitary, so
+// u = 1 + conj(U) is one: conj(u) / u = (1 + U) / (1 + 1 / U) = U.  u lies in Fp6 exactly when
+// U = 1 (U = conj(U) = 1 / U means U^2 = 1, and the cyclotomic subgroup has odd order).
+template <int NT, class O>
+__device__ __forceinline__ fp_t final_exp_gu(O& o, const fp_t& x, fp_t* nrm, int team, bool own, bool* zero) {
+  fp_t G;
+  const fp_t N = tm_easy_norm(o, x, &G);
+  const fp_t n = o.norm2(N);  // the same on every lane of the team
+  *zero = fp_is_zero(n);
+  if (team < NT && o.c == 0) nrm[team] = fp_select(own && !*zero, fp_one(), n);
+  __syncthreads();
+  const fp_t ninv = tm_block_inv<NT>(nrm, team);
+  const fp_t U = tm_final_exp_cyc(o, tm_easy_finish(o, x, G, N, ninv));
+  const fp_t u = o.conj(U);
+  return fp_select(o.cc == 0, u, fp_add(u, fp_one()));
+}
 
 
 // A group's verdict bits from its u (bls_team.h tm_final_exp_u; pairing value conj(u)/u):
@@ -35,6 +71,7 @@ __global__ void BGV_KATTR k_final(const bgv_dgroup* __restrict__ groups, uint32_
                                   int32_t* __restrict__ verdict, fp12_t* __restrict__ gprod,
                                   fp12_t* __restrict__ gu, const fp12_t* __restrict__ gu1) {
   __shared__ fp_t lds[BGV_FINAL_TEAMS][2 * BGV_TEAM_COMPS];
+  __shared__ fp_t nrm[BGV_FINAL_TEAMS];
   __shared__ uint32_t lens[BGV_FINAL_TEAMS];
   const int team = threadIdx.x / BGV_TEAM, c = threadIdx.x % BGV_TEAM;
   const int cc = c < BGV_TEAM_COMPS ? c : c - 4;
@@ -62,10 +99,11 @@ __global__ void BGV_KATTR k_final(const bgv_dgroup* __restrict__ groups, uint32_
   }
   // the group's Miller-loop product, kept for cross-process partials (bgv_verify_partial)
   if (gprod && gi < ngroups && c < BGV_TEAM_COMPS) reinterpret_cast<fp_t*>(gprod + gi)[fi] = x;
-  const fp_t u = tm_final_exp_u(o, x);
+  bool zero;
+  const fp_t u = final_exp_gu<BGV_FINAL_TEAMS>(o, x, nrm, team, gi < ngroups, &zero);
   if (gu && gi < ngroups && c < BGV_TEAM_COMPS) reinterpret_cast<fp_t*>(gu + gi)[fi] = u;
   const int32_t v = verdict_bits(o, u, g, gu1, fi);
-  if (gi < ngroups && c == 0) verdict[gi] = v;
+  if (gi < ngroups && c == 0) verdict[gi] = zero ? 0 : v;
 }
 
 // k_final on teams of 12 lanes, five per wave (lanes 60..63 run a sixth, idle team on LDS
@@ -81,6 +119,7 @@ __global__ void BGV_KATTR k_final(const bgv_dgroup* __restrict__ groups, uint32_
 }  // extern "C"
 __device__ __forceinline__ void final12_body(BGV_FINAL12_ARGS) {
   __shared__ fp_t lds[BGV_FINAL12_TEAMS + 1][2 * BGV_TEAM_COMPS];
+  __shared__ fp_t nrm[BGV_FINAL12_TEAMS];
   __shared__ uint32_t lens[BGV_FINAL12_TEAMS + 1];
   const int team = threadIdx.x / BGV_TEAM_COMPS, c = threadIdx.x % BGV_TEAM_COMPS;
   const uint32_t gi = blockIdx.x * BGV_FINAL12_TEAMS + team;
@@ -117,10 +156,11 @@ __device__ __forceinline__ void final12_body(BGV_FINAL12_ARGS) {
   }
   if (gpkp) x = o.mul(x, uni ? reinterpret_cast<const fp_t*>(gpkp + gi)[fi] : one_c);  // grid-uniform branch
   if (gprod && live) reinterpret_cast<fp_t*>(gprod + gi)[fi] = x;
-  const fp_t u = tm_final_exp_u(o, x);
+  bool zero;
+  const fp_t u = final_exp_gu<BGV_FINAL12_TEAMS>(o, x, nrm, team, live, &zero);
   if (gu && live) reinterpret_cast<fp_t*>(gu + gi)[fi] = u;
   const int32_t v = verdict_bits(o, u, g, gu1, fi);
-  if (live && c == 0) verdict[gi] = v;
+  if (live && c == 0) verdict[gi] = zero ? 0 : v;
 }
 
 // Weighted tests (BGV_GROUP_WEIGHTED) after k_final12 of a retry round: the first w <= n_slots

@@ -37,6 +37,27 @@ struct tm_dev_ops_t {
     __syncthreads();
     return r;
   }
+  // x in the cyclotomic subgroup (bls_team.h tm_cyc_sqr_lane)
+  __device__ fp_t cyc_sqr(const fp_t& x) {
+    if (c < BGV_TEAM_COMPS) A[c] = x;
+    __syncthreads();
+    const fp_t r = tm_cyc_sqr_lane(cc, A);
+    __syncthreads();
+    return r;
+  }
+  // n = N0^2 + N1^2 of an N in Fp2 (bls_team.h tm_easy_norm), on every lane of the team
+  __device__ fp_t norm2(const fp_t& x) {
+    if (c < BGV_TEAM_COMPS) A[c] = x;
+    __syncthreads();
+    const fp_t n0 = A[0], n1 = A[1];
+    __syncthreads();
+    return fp_add(fp_sqr(n0), fp_sqr(n1));
+  }
+  // conj2(N) ninv as a team value: components 0 and 1, zeros above
+  __device__ fp_t scale2(const fp_t& x, const fp_t& ninv) {
+    const fp_t s = fp_mul(x, ninv);
+    return fp_select(cc == 0, fp_select(cc == 1, fp_zero(), fp_neg(s)), s);
+  }
   __device__ fp_t line(const fp2_t& l0, const fp2_t& l1, const fp2_t& l3) { return tm_line_lane(cc, l0, l1, l3); }
   __device__ fp_t mul_line(const fp_t& x, const fp2_t& l0, const fp2_t& l1, const fp2_t& l3) {
     if (c < BGV_TEAM_COMPS) A[c] = x;

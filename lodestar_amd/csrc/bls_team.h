@@ -17,13 +17,27 @@
 // are exchanged through LDS.  Per lane that is 12 x 196 + 196 u32 MACs against
 // 54 full Fp products (~21k MACs) for the one-lane tower product.
 //
-// Final exponentiation without an inversion.  f^((p^12-1)/r) == 1 iff
-// f^((p^2+1) h) lies in Fp6 (the kernel of x -> x^(p^6-1)), h = (p^4-p^2+1)/r.
-// Modulo Fp6*, conj(a) = a^(p^6) = N(a)/a is an inverse of a for EVERY a, and the
-// Frobenius maps are automorphisms, so the x-chain of the hard part
-// (bls_pairing.h final_exp) runs unchanged on representatives with generic
-// squarings, starting from t = frob2(f) * f; the verdict is "odd w-coefficients of
-// the result are zero".  The easy part's Fp12 inversion disappears.
+// Two final exponentiations share the hard part's x-chain (bls_pairing.h final_exp).
+//
+// The closing teams (k_final12, k_final) run the whole of it: the easy part
+// t = f^((p^6-1)(p^2+1)), then the chain on t with Granger-Scott squarings
+// (tm_cyc_sqr_lane: 4 double-width products and one reduction per lane against the
+// generic squaring's 7 + 1; 315 of the chain's ~345 operations are squarings).  The
+// easy part's Fp12 inversion is one Fp inversion of the norm n (tm_easy_norm), and a
+// block shares that one among its teams: Montgomery's trick over the teams' n and
+// one exponentiation spread over the wavefront (tm_batch_inv_core, bgv_wfp.h).  The
+// result U = f^(3 (p^12-1)/r) is the pairing value cubed; the teams store
+// u = 1 + conj(U), whose conj(u)/u is U, so every reader of u (below) is served.
+//
+// The residue engine of k_final_fold runs it without an inversion.
+// f^((p^12-1)/r) == 1 iff f^((p^2+1) h) lies in Fp6 (the kernel of x -> x^(p^6-1)),
+// h = (p^4-p^2+1)/r.  Modulo Fp6*, conj(a) = a^(p^6) = N(a)/a is an inverse of a for
+// EVERY a, and the Frobenius maps are automorphisms, so the x-chain runs unchanged on
+// representatives with generic squarings, starting from t = frob2(f) * f
+// (tm_final_exp_u); the verdict is "odd w-coefficients of the result u are zero", and
+// the pairing value is conj(u)/u.  That engine has one block per group and nothing to
+// share an inversion with, and a squaring there costs its two base extensions whatever
+// its products are, so the cyclotomic formulas would buy it nothing.
 #pragma once
 #include "bls_pairing.h"
 
@@ -130,6 +144,69 @@ BGV_HD fp_t tm_sqr_lane(int c, const fp_t* A) {
   const fp_t P = e ? fp_add_norm(x0, x0) : fp_add_norm(x0, x1);
   const fp_t Q = e ? x1 : fp_sub_nr(x0, x1);
   wide_mac(t, fp_select(even, fp_zero(), P), Q);
+  return wide_redc(t);
+}
+
+// Granger-Scott squaring of an element of the cyclotomic subgroup (any value that went through
+// the easy part), coefficient c = 2k + e.  Fp4 = Fp2[s], s = w^3, s^2 = xi; A = (f0, f3),
+// B = (f1, f4), C = (f2, f5):  f^2 = (3 A^2 - 2 conj A) + (3 s C^2 + 2 conj B) w + (3 B^2 - 2 conj C) w^2,
+//   h0 = 3 (f0^2 + xi f3^2) - 2 f0      h3 = 6 f0 f3 + 2 f3
+//   h1 = 6 xi f2 f5         + 2 f1      h4 = 3 (f2^2 + xi f5^2) - 2 f4
+//   h2 = 3 (f1^2 + xi f4^2) - 2 f2      h5 = 6 f1 f4 + 2 f5
+// With (x, y) the lane's Fp4 pair, x = x0 + x1 u, y = y0 + y1 u:
+//   x^2 + xi y^2  re (x0 + x1)(x0 - x1) + (y0 + y1)(y0 - y1) - 2 y0 y1
+//                 im 2 x0 x1 + (y0 + y1)(y0 - y1) + 2 y0 y1
+//   2 x y         re 2 x0 y0 - 2 x1 y1                    im 2 x0 y1 + 2 y0 x1
+//   2 xi x y      re 2 x0 (y0 - y1) - 2 y0 x1 - 2 y1 x1   im 2 x0 y0 + 2 x0 y1 + 2 x1 (y0 - y1)
+// Every lane runs the same three double-width products X Y (the 2xy lanes multiply zeros in the
+// third) plus its own coefficient times the constant -+2, and one reduction: 4 x 196 + 196 MACs
+// against tm_sqr_lane's 7 x 196 + 196, and two short operand chains per product where the
+// generic squaring forms and selects a dozen.  X = V[a] + V[b] limb-wise (V = x0, x1, y0, y1; a
+// doubling is a = b), Y = 3 (V[a] - V[b] + 2p) with either term and the 2p maskable, carried.
+// The lane reads the four Fp values of its pair and its own coefficient, nothing else.
+// Recipe digits, low to high: X a, X b, Y a (4: none), Y b (4: none), 2p.
+// Bounds: values <= 2p with limbs < 2^28.  X < 4p, limbs < 2^29; Y <= 12p, limbs < 2^28 (the
+// chain's 3 d + carry stays inside 32 bits: |d| <= 2^29): a product is < 48 p^2 and < 2^57 per
+// column term.  Three of them, the linear product (< 4 p^2, < 2^56 per term) and the reduction's
+// rows (< 2^56 per term), 14 terms each: columns < 14 (3 2^57 + 2^57) = 2^62.9 < 2^63, and
+// T < 148 p^2, so the result is < p (1 + 148 p / 2^392) < 1.06 p.
+BGV_HD fp_t tm_cyc_y(const fp_t& a, uint32_t ma, const fp_t& b, uint32_t mb, uint32_t mk) {
+  fp_t r;
+  int32_t cy = 0;
+  BGV_UNROLL for (int l = 0; l < NL; ++l) {
+    const int32_t d = (int32_t)(a.v[l] & ma) - (int32_t)(b.v[l] & mb) + (int32_t)(p2_limb(l) & mk);
+    const int32_t s = 3 * d + cy;
+    r.v[l] = l < NL - 1 ? (uint32_t)s & LMASK : (uint32_t)s;
+    cy = s >> LBITS;
+  }
+  return r;
+}
+
+BGV_HD fp_t tm_cyc_sqr_lane(int c, const fp_t* A) {
+  const int k = c >> 1, e = c & 1;
+  // per k: the pair's first coefficient i (the second is i + 3) and the form: 0 x^2 + xi y^2,
+  // 1 2xy, 2 2 xi x y; the linear term is -2 f_k for the first form, +2 f_k for the others
+  const uint32_t kPair = 0x120120, kForm = 0x101020;
+  const uint32_t kRec[3][2][3] = {{{0x11010, 0x13232, 0x13422}, {0x04100, 0x13232, 0x04322}},
+                                  {{0x04200, 0x11433, 0x04400}, {0x04300, 0x04122, 0x04400}},
+                                  {{0x13200, 0x11422, 0x11433}, {0x04200, 0x04300, 0x13211}}};
+  const int i = (kPair >> (4 * k)) & 0xf, form = (kForm >> (4 * k)) & 0xf;
+  static_assert(14ull * (3ull * (1ull << 57) + (1ull << 56) + (1ull << 56)) < (1ull << 63), "column bound");
+  uint64_t t[2 * NL];
+  BGV_UNROLL for (int q = 0; q < 2 * NL; ++q) t[q] = 0;
+  // (a loop: unrolled, k_final12 spills 74 registers instead of 7 and the headline reads
+  // 2.812-2.815 against 2.826-2.828 M sets/s, profiles/cyc_closing/)
+  BGV_NO_UNROLL for (int p = 0; p < 3; ++p) {
+    const uint32_t r = kRec[form][e][p];
+    // V index v -> component: x0, x1 = 2i, 2i + 1; y0, y1 = 2i + 6, 2i + 7
+    const int xa = r & 0xf, xb = (r >> 4) & 0xf, ya = (r >> 8) & 0xf, yb = (r >> 12) & 0xf;
+    const fp_t X = fp_add_nr(A[2 * i + (xa & 1) + 6 * (xa >> 1)], A[2 * i + (xb & 1) + 6 * (xb >> 1)]);
+    const fp_t Y = tm_cyc_y(A[2 * i + (ya & 1) + 6 * ((ya >> 1) & 1)], ya < 4 ? ~0u : 0u,
+                            A[2 * i + (yb & 1) + 6 * ((yb >> 1) & 1)], yb < 4 ? ~0u : 0u, (r >> 16) ? ~0u : 0u);
+    wide_mac(t, X, Y);
+  }
+  const fp_t two = fp_dbl(fp_one());
+  wide_mac(t, A[c], fp_select(form == 0, two, fp_neg(two)));
   return wide_redc(t);
 }
 
@@ -533,6 +610,86 @@ BGV_HD bool tm_final_exp_is_one(O& o, const E& f) {
   return o.is_fp6(tm_final_exp_u(o, f));
 }
 
+// The closing kernels' final exponentiation (k_final12, k_final): the easy part with its Fp12
+// inversion, then the same x-chain with cyclotomic squarings.  The inversion is one Fp inversion
+// of the Fp norm, which a block shares among its teams (tm_batch_inv):
+//   D = f conj(f) in Fp6,  E = D^(p^2) D^(p^4),  N = D E in Fp2 (the norm Fp6 -> Fp2),
+//   n = N0^2 + N1^2 in Fp,  1/f = conj(f) E conj2(N) / n.
+// tm_easy_norm returns N (components 0, 1) and G = conj(f) E; with 1/n, tm_easy_finish gives
+// t = f^((p^6 - 1)(p^2 + 1)).  O supplies norm2 (n of N) and scale2 (conj2(N) ninv as an element).
+template <class O, class E>
+BGV_HD E tm_easy_norm(O& o, const E& f, E* G) {
+  const E cf = o.conj(f);
+  const E D = o.mul(f, cf);
+  const E D2 = o.frob2(D);
+  const E Ee = o.mul(D2, o.frob2(D2));
+  *G = o.mul(cf, Ee);
+  return o.mul(D, Ee);
+}
+
+template <class O, class E>
+BGV_HD E tm_easy_finish(O& o, const E& f, const E& G, const E& N, const fp_t& ninv) {
+  const E finv = o.mul(G, o.scale2(N, ninv));
+  const E g = o.mul(o.conj(f), finv);  // f^(p^6 - 1)
+  return o.mul(o.frob2(g), g);
+}
+
+// a^x in the cyclotomic subgroup (bls_pairing.h cyclotomic_pow_x)
+template <class O, class E>
+BGV_HD E tm_cyc_pow_x(O& o, const E& a) {
+  const uint64_t X = BGV_X_ABS;
+  E r = a;
+  BGV_NO_UNROLL for (int i = 62; i >= 0; --i) {
+    r = o.cyc_sqr(r);
+    if ((X >> i) & 1) r = o.mul(r, a);
+  }
+  return o.conj(r);  // x < 0
+}
+
+// U = t^(3 (p^4 - p^2 + 1) / r) for t out of the easy part: tm_final_exp_u's chain, which is
+// final_exp's (bls_pairing.h).  U is the pairing value to the power BGV_FINAL_EXP_CHAIN_FACTOR.
+#define BGV_FINAL_EXP_CHAIN_FACTOR 3
+template <class O, class E>
+BGV_HD E tm_final_exp_cyc(O& o, const E& t) {
+  E a = o.mul(tm_cyc_pow_x(o, t), o.conj(t));      // t^(x-1)
+  a = o.mul(tm_cyc_pow_x(o, a), o.conj(a));        // t^((x-1)^2)
+  a = o.mul(tm_cyc_pow_x(o, a), o.frob(a));        // ^(x+p)
+  E b = tm_cyc_pow_x(o, tm_cyc_pow_x(o, a));       // a^(x^2)
+  b = o.mul(o.mul(b, o.frob2(a)), o.conj(a));      // a^(x^2 + p^2 - 1)
+  const E t3 = o.mul(o.cyc_sqr(t), t);             // t^3
+  return o.mul(b, t3);
+}
+
+// Montgomery's trick over NT nonzero values: out[i] = 1 / v[i] with one inversion (inv) and
+// 3 (NT - 1) products.
+template <int NT, class INV>
+BGV_HD void tm_batch_inv_core(const fp_t* v, fp_t* out, INV inv) {
+  fp_t pre[NT];
+  pre[0] = v[0];
+  BGV_UNROLL for (int i = 1; i < NT; ++i) pre[i] = fp_mul(pre[i - 1], v[i]);
+  fp_t r = inv(pre[NT - 1]);
+  BGV_UNROLL for (int i = NT - 1; i >= 1; --i) {
+    out[i] = fp_mul(r, pre[i - 1]);
+    r = fp_mul(r, v[i]);
+  }
+  out[0] = r;
+}
+
+// The same with zeros allowed: a zero takes part as 1 (its out entry is 1) and sets its bit of the
+// returned mask, so it never spoils the other inverses.
+template <int NT, class INV>
+BGV_HD uint32_t tm_batch_inv(const fp_t* v, fp_t* out, INV inv) {
+  fp_t w[NT];
+  uint32_t zero = 0;
+  for (int i = 0; i < NT; ++i) {
+    const bool z = fp_is_zero(v[i]);
+    zero |= z ? 1u << i : 0u;
+    w[i] = fp_select(z, v[i], fp_one());
+  }
+  tm_batch_inv_core<NT>(w, out, inv);
+  return zero;
+}
+
 // Host emulation of a team (tests): all 12 components in one value, every op
 // runs the lane functions above for each lane.
 struct tm_emu_t {
@@ -548,6 +705,19 @@ struct tm_emu_ops {
   BGV_HD tm_emu_t sqr(const tm_emu_t& a) {
     tm_emu_t r;
     for (int c = 0; c < BGV_TEAM_COMPS; ++c) r.c[c] = tm_sqr_lane(c, a.c);
+    return r;
+  }
+  BGV_HD tm_emu_t cyc_sqr(const tm_emu_t& a) {
+    tm_emu_t r;
+    for (int c = 0; c < BGV_TEAM_COMPS; ++c) r.c[c] = tm_cyc_sqr_lane(c, a.c);
+    return r;
+  }
+  BGV_HD fp_t norm2(const tm_emu_t& N) { return fp_add(fp_sqr(N.c[0]), fp_sqr(N.c[1])); }
+  BGV_HD tm_emu_t scale2(const tm_emu_t& N, const fp_t& ninv) {
+    tm_emu_t r;
+    for (int c = 0; c < BGV_TEAM_COMPS; ++c) r.c[c] = fp_zero();
+    r.c[0] = fp_mul(N.c[0], ninv);
+    r.c[1] = fp_neg(fp_mul(N.c[1], ninv));
     return r;
   }
   BGV_HD tm_emu_t line(const fp2_t& l0, const fp2_t& l1, const fp2_t& l3) {
