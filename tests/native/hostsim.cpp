@@ -365,6 +365,24 @@ int hs_tcurve_check(const uint8_t* msg32, uint64_t k, int* bad_out) {
   if (!jac_eq(h_team, h_lane)) return 0;
   return jac_eq(tc_mul_glv_host(h_lane, k), jac_mul_glv(h_lane, k)) ? 1 : 0;
 }
+// k_prep_wide's plane 2 (bgv_k_prep.hip) on a decoded affine point: banks 0 and 4 = P,
+// tc_mul_x_abs on the generic-case addition programs, tc_to_jac, psi(P) == -[|x|]P.
+// *bad_out = the exceptional-addition flag, *plain_out = the verdict of the team's chain alone;
+// returns the kernel's verdict (the one-lane g2_in_subgroup when the flag is set)
+int hs_team_subgroup(const uint8_t* aff, int* bad_out, int* plain_out) {
+  static const uint8_t tab[TCP_TABLE_BYTES] = TCP_TABLE_INIT;
+  static fp_t S[TCP_NSLOT];
+  const g2_jac p = jac_from_aff(in_g2(aff));
+  tc_host_init(S);
+  tc_put(S, 0, p);
+  tc_put(S, 4, p);
+  tc_host_engine e{tab, S};
+  const int a = tc_to_jac(e, tc_mul_x_abs(e));
+  const int plain = jac_eq(g2_psi(p), jac_neg(tc_get(S, a))) ? 1 : 0;
+  *bad_out = e.bad ? 1 : 0;
+  *plain_out = plain;
+  return e.bad ? (g2_in_subgroup(p) ? 1 : 0) : plain;
+}
 // the latency path's team loop (bgv_tmiller.h: table-driven twist-point rounds + team Fp12)
 // the latency path's G1 schedule (bgv_tg1.h tg1_mul_glv, projective programs) against the
 // one-lane jac_mul_glv, P handed in Jacobian with Z != 1: 1 when the points agree
