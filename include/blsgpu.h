@@ -253,6 +253,45 @@ int bgv_verify_bits_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const
  * 96-byte uncompressed encoding (0x40 for infinity).  Codes as the set checks above. */
 int bgv_aggregate_committee_bits(bgv_ctx* ctx, uint32_t id, const uint8_t* bits, uint32_t n_bits, uint8_t out96[96]);
 
+/* One bitfield over several committees: the attestation format since EIP-7549, where
+ * committee_bits selects up to MAX_COMMITTEES_PER_SLOT committees of a slot and aggregation_bits is
+ * laid over them, concatenated in ascending committee order (the spec's get_attesting_indices:
+ * a running committee_offset, member i of a committee takes part iff
+ * aggregation_bits[committee_offset + i]).  Committee c of the list owns the bits
+ * [off_c, off_c + n_c), off_c = n_0 + ... + n_{c-1}; its member p takes part iff bit off_c + p is
+ * set (SSZ bit order).  The list is taken as given: a repeated id counts its selected members
+ * again, as an index list with repeats does; ascending order, and the consensus rule that every
+ * listed committee has an attester, are the caller's business.  Every committee takes its own
+ * shorter side (its selected members, or its total minus the unselected ones).
+ * n_committees == 0: the set's own pk_indices / pk_bytes count; n_committees == 1 is exactly
+ * bgv_pkbits {committees[0], n_bits, bits}. */
+#define BGV_MAX_SET_COMMITTEES 64 /* MAX_COMMITTEES_PER_SLOT */
+#define BGV_MAX_SPAN_BITS 131072  /* 64 x 2048, the spec's bound on aggregation_bits */
+typedef struct {
+  const uint32_t* committees; /* n_committees ids, in bitfield order */
+  uint32_t n_committees;      /* 0: the set's own pk_indices / pk_bytes count */
+  uint32_t n_bits;            /* sum of the listed committees' lengths */
+  const uint8_t* bits;        /* ceil(n_bits / 8) bytes, SSZ bit order */
+} bgv_pkspan;
+
+/* bgv_verify_bits / bgv_verify_bits_async with spans[i] beside sets[i] (spans may be NULL:
+ * bgv_verify).  A job's code from the host's argument checks of a span set, in this order: an
+ * unknown or dropped id anywhere in the list -BGV_E_BAD_INDEX; n_committees >
+ * BGV_MAX_SET_COMMITTEES, n_bits > BGV_MAX_SPAN_BITS or n_bits other than the sum of the listed
+ * committees' lengths -BGV_E_ARG; a set bit at or past n_bits in the last byte -BGV_E_ARG; no bit
+ * set -BGV_E_EMPTY_AGGREGATE; a listed committee that holds a marked key -BGV_E_BAD_INDEX.
+ * Everything else is the call with the expanded index list. */
+int bgv_verify_spans(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                     const bgv_pkspan* spans, int mode, int32_t* out_job_codes, bgv_stats* stats);
+int bgv_verify_spans_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                           const bgv_pkspan* spans, int mode, int32_t* out_job_codes, bgv_stats* stats,
+                           bgv_done_fn done, void* user);
+
+/* Parity hook: the aggregate of a span's selected members through the verify path's own kernel
+ * (k_pk_agg_span, the sides the layout would take; k_pk_agg_bits for one committee), 96-byte
+ * uncompressed encoding (0x40 for infinity).  Codes as the set checks above. */
+int bgv_aggregate_span(bgv_ctx* ctx, const bgv_pkspan* span, uint8_t out96[96]);
+
 /* Parity hook for bls.PublicKey.aggregate + toBytes(uncompressed)
  * (chain/bls/utils.ts:5-16, multithread/index.ts:160): sum of cached pubkeys,
  * 96-byte uncompressed ZCash encoding (0x40 flag for infinity). */

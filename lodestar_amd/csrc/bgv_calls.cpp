@@ -259,24 +259,23 @@ int bgv_aggregate_pubkeys(bgv_ctx* c, const uint32_t* idx, size_t n, uint8_t out
   return sc.sync();
 }
 
-int bgv_aggregate_committee_bits(bgv_ctx* c, uint32_t id, const uint8_t* bits, uint32_t n_bits, uint8_t out96[96]) {
-  if (!c || !out96 || (n_bits && !bits)) return -BGV_E_ARG;
+// The aggregate of one committee or span set (pk names it for set 0) through the call's own
+// checks and layout, then k_pk_agg_bits / k_pk_agg_span and pk_sum
+static int aggregate_one(bgv_ctx* c, PkForm pk, uint8_t out96[96]) {
   std::shared_lock<std::shared_mutex> clk(c->cache_mu);
   if (c->closed) return -BGV_E_CLOSED;
-  // one committee set through the call's own checks and layout, then k_pk_agg_bits / pk_sum
   const uint8_t zero[96] = {0};
   bgv_set st{};
   st.sig_len = 96;
   st.msg = zero;
   st.sig = zero;
-  const bgv_pkbits pb{id, n_bits, bits};
   const bgv_job jb{0, 1, 0};
   Call call;
   call.setcom.assign(1, SetCommittee{});
   int32_t code = 2;
   {
     std::shared_lock<std::shared_mutex> mlk(c->com_mu);
-    if (host_job_code(c, jb, &st, &code, &pb, &call) != BGV_OK) return -BGV_E_ARG;
+    if (host_job_code(c, jb, &st, &code, pk, &call) != BGV_OK) return -BGV_E_ARG;
   }
   if (code != 2) return code;
   Layout L;
@@ -297,10 +296,23 @@ int bgv_aggregate_committee_bits(bgv_ctx* c, uint32_t id, const uint8_t* bits, u
   HIPCHK(hipMemcpyAsync(di, L.idx.data(), 4 * L.idx.size(), hipMemcpyHostToDevice, d.stream));
   HIPCHK(hipMemcpyAsync(di + L.idx.size(), &list, 4, hipMemcpyHostToDevice, d.stream));
   HIPCHK(hipMemcpyAsync(ds, L.slots.data(), sizeof(bgv_dslot), hipMemcpyHostToDevice, d.stream));
-  HIPCHK(bgv_launch_aggregate_bits(ds, di, di + L.idx.size(), !L.com_team.empty(), d.com_dir, d.com_pool, d.cache,
-                                   dagg, dout, d.stream));
+  const bool span = !(L.span_team.empty() && L.span_wave.empty());
+  HIPCHK(bgv_launch_aggregate_bits(ds, di, di + L.idx.size(), !(L.com_team.empty() && L.span_team.empty()), span,
+                                   d.com_dir, d.com_pool, d.cache, dagg, dout, d.stream));
   HIPCHK(hipMemcpyAsync(out96, dout, 96, hipMemcpyDeviceToHost, d.stream));
   return sc.sync();
+}
+
+int bgv_aggregate_committee_bits(bgv_ctx* c, uint32_t id, const uint8_t* bits, uint32_t n_bits, uint8_t out96[96]) {
+  if (!c || !out96 || (n_bits && !bits)) return -BGV_E_ARG;
+  const bgv_pkbits pb{id, n_bits, bits};
+  return aggregate_one(c, PkForm(&pb), out96);
+}
+
+int bgv_aggregate_span(bgv_ctx* c, const bgv_pkspan* span, uint8_t out96[96]) {
+  if (!c || !out96 || !span || !span->committees || (span->n_bits && !span->bits)) return -BGV_E_ARG;
+  if (span->n_committees == 0) return -BGV_E_EMPTY_AGGREGATE;  // names no committee
+  return aggregate_one(c, PkForm(span), out96);
 }
 
 int bgv_hash_to_g2(bgv_ctx* c, const uint8_t* msgs, const uint32_t* lens, size_t n, uint8_t* out192) {

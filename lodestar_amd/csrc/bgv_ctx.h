@@ -287,8 +287,7 @@ struct Device {
 // units: CallPlan, bgv_retry_plan.h) and how its caller hears of the end.
 struct Call : CallPlan {
   const bgv_set* sets = nullptr;
-  const bgv_pkbits* pkbits = nullptr;                   // per set, or null (bgv_verify_bits)
-  std::vector<SetCommittee> setcom;                     // per set once checked (empty without pkbits)
+  std::vector<SetCommittee> setcom;                     // per set once checked (empty for bgv_verify)
   std::vector<std::shared_ptr<CommitteeRec>> com_refs;  // the committees the layout names
   int32_t* out = nullptr;
   bgv_stats* stats_out = nullptr;
@@ -398,8 +397,8 @@ int exec_reserve_groups(Exec& x, uint32_t groups);
 int exec_reserve_lines(Exec& x, bgv_dev_batch& b);
 int exec_reserve_line_pairs(Exec& x, bgv_dev_batch& b, uint32_t need);  // a retry round's team pairs
 bgv_dev_batch make_batch(Device& d, Exec& x, uint32_t nslots, uint32_t ngroups);
-int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code,
-                  const bgv_pkbits* pkbits = nullptr, Call* call = nullptr);
+int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code, PkForm pk = PkForm(),
+                  Call* call = nullptr);
 void fp12_one_bytes(uint8_t out[576]);
 
 #pragma GCC visibility pop

@@ -17,6 +17,27 @@
 #include "bgv_layout.h"
 #include "bgv_pk_bits.h"
 
+// How a call names its sets' pubkeys beside the sets: a bgv_pkbits per set (bgv_verify_bits), a
+// bgv_pkspan per set (bgv_verify_spans), or neither (bgv_verify).
+struct PkForm {
+  const bgv_pkbits* bits = nullptr;
+  const bgv_pkspan* spans = nullptr;
+  PkForm() = default;
+  PkForm(const bgv_pkbits* b) : bits(b) {}
+  PkForm(const bgv_pkspan* s) : spans(s) {}
+  explicit operator bool() const { return bits || spans; }
+  // set i names committees, not its own pk_indices / pk_bytes
+  bool is_com(size_t i) const {
+    return bits ? bits[i].committee != BGV_NO_COMMITTEE : spans && spans[i].n_committees != 0;
+  }
+  PkForm from(size_t i) const {  // for the sets from set i on
+    PkForm f;
+    f.bits = bits ? bits + i : nullptr;
+    f.spans = spans ? spans + i : nullptr;
+    return f;
+  }
+};
+
 namespace {
 
 inline size_t env_size(const char* name, size_t dflt, size_t lo) {
@@ -106,6 +127,9 @@ struct SetCommittee {
   uint32_t n = 0;  // members (= n_bits)
   uint32_t k = 0;  // bits set
   const uint8_t* bits = nullptr;
+  // a span over two or more committees (bgv_pkspan): handle, n, k of each, in bitfield order;
+  // handle above is then the first one's, n the bitfield's length and k its set bits
+  std::vector<pkb_part> parts;
 };
 // The argument checks of one committee set (blsgpu.h bgv_verify_bits): 2 and *out filled when it
 // goes to the device, else the code its job gets.  ci: the live committee of pb.committee, or
@@ -120,6 +144,43 @@ inline int32_t committee_set_check(const CommitteeInfo* ci, const bgv_pkbits& pb
   if (k == 0) return -BGV_E_EMPTY_AGGREGATE;
   if (ci->bad) return -BGV_E_BAD_INDEX;
   *out = SetCommittee{ci->handle, ci->n, k, pb.bits};
+  return 2;
+}
+// The same for a span set (blsgpu.h bgv_verify_spans), in committee_set_check's order with the
+// whole list in place of the one committee.  look(id, &ci): whether committee id is live, and
+// then the host's mirror of it.  One listed committee is committee_set_check itself, so such a
+// span lays out the very slot bgv_verify_bits does.
+template <class Look>
+inline int32_t span_set_check(Look look, const bgv_pkspan& sp, SetCommittee* out) {
+  CommitteeInfo ci{};
+  if (sp.n_committees == 1) {
+    const bool live = look(sp.committees[0], &ci);
+    return committee_set_check(live ? &ci : nullptr, bgv_pkbits{sp.committees[0], sp.n_bits, sp.bits}, out);
+  }
+  uint64_t total = 0;
+  bool bad = false;
+  std::vector<pkb_part> parts;
+  parts.reserve(std::min<uint32_t>(sp.n_committees, BGV_MAX_SET_COMMITTEES));
+  for (uint32_t c = 0; c < sp.n_committees; ++c) {
+    if (!look(sp.committees[c], &ci)) return -BGV_E_BAD_INDEX;
+    total += ci.n;
+    bad = bad || ci.bad;
+    if (c < BGV_MAX_SET_COMMITTEES) parts.push_back(pkb_part{ci.handle, ci.n, 0u});
+  }
+  if (sp.n_committees > BGV_MAX_SET_COMMITTEES || sp.n_bits > BGV_MAX_SPAN_BITS || sp.n_bits != total)
+    return -BGV_E_ARG;
+  const uint32_t nbytes = (sp.n_bits + 7u) / 8u;
+  if ((sp.n_bits & 7u) && (sp.bits[nbytes - 1] >> (sp.n_bits & 7u))) return -BGV_E_ARG;
+  uint32_t k = 0, off = 0;
+  for (pkb_part& p : parts) {
+    p.k = pkb_span_count(sp.bits, nbytes, off, p.n);
+    k += p.k;
+    off += p.n;
+  }
+  if (k == 0) return -BGV_E_EMPTY_AGGREGATE;
+  if (bad) return -BGV_E_BAD_INDEX;
+  *out = SetCommittee{parts[0].handle, sp.n_bits, k, sp.bits};
+  out->parts = std::move(parts);
   return 2;
 }
 
@@ -140,11 +201,14 @@ struct Layout {
   // the committee slots (BGV_SLOT_PK_COMMITTEE) k_pk_agg_bits sums: those whose chosen side has
   // at most BGV_PK_TEAM_MAX terms (a 16-lane team each), and the others (a wave each)
   std::vector<uint32_t> com_team, com_wave;
+  // the same for the span slots (BGV_SLOT_PK_SPAN) k_pk_agg_span sums, by the span's term count M
+  std::vector<uint32_t> span_team, span_wave;
 };
 
 // A call's slot as it stands in a merged super-batch (bgv_sched.cpp run_pass1): after slot_base
 // slots, ib words of the index array, pb 96-byte pubkey records and gb groups of earlier calls.
-// A committee slot's run (handle and bit words) lies in the index array like a run of indices.
+// A committee slot's run (handle and bit words; a span's records, which hold handles and no
+// offsets) lies in the index array like a run of indices.
 inline bgv_dslot rebase_slot(bgv_dslot s, uint32_t slot_base, uint32_t ib, uint32_t pb, uint32_t gb) {
   s.hsrc += slot_base;
   if (s.flags & (BGV_SLOT_PK_CACHED | BGV_SLOT_PK_COMMITTEE)) s.pk_off += ib;
@@ -218,7 +282,15 @@ struct Builder {
     s.n_pk = st.n_pk;
     s.sig_len = st.sig_len;
     s.group = open_group;
-    if (sc && sc->handle != BGV_NO_COMMITTEE) {
+    if (sc && !sc->parts.empty()) {
+      // the span's run (bgv_pk_bits.h pkb_span_build) in the call's index array
+      s.flags = BGV_SLOT_PK_COMMITTEE | BGV_SLOT_PK_SPAN;
+      s.n_pk = sc->k;
+      s.pk_off = (uint32_t)L.idx.size();
+      const uint32_t m = pkb_span_build(sc->parts.data(), (uint32_t)sc->parts.size(), sc->bits, (sc->n + 7u) / 8u,
+                                        [&](uint32_t v) { L.idx.push_back(v); });
+      (m <= BGV_PK_TEAM_MAX ? L.span_team : L.span_wave).push_back((uint32_t)L.slots.size());
+    } else if (sc && sc->handle != BGV_NO_COMMITTEE) {
       // the handle, then the bitfield as 32-bit little-endian words, in the call's index array
       const bool comp = pkb_use_complement(sc->n, sc->k);
       s.flags = BGV_SLOT_PK_COMMITTEE | (comp ? BGV_SLOT_PK_COMPLEMENT : 0u);

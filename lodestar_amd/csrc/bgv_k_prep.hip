@@ -8,6 +8,9 @@
 //   k_pk_agg_bits  (only when a call holds committee-bitfield sets, BGV_SLOT_PK_COMMITTEE) the
 //              selected members of a device-resident committee, or the unselected ones subtracted
 //              from its total, on a 16-lane team or a whole wave per set (bgv_pk_bits.h)
+//   k_pk_agg_span  (only when a call holds span sets, BGV_SLOT_PK_SPAN) the same for one bitfield
+//              laid over several committees: every committee's shorter side and the totals of
+//              the complement ones as ONE term list, walked by rank on a team or a wave per set
 //   k_prep_a / k_prep_team   the latency path for small calls (bgv_latency_max): the same
 //              work over two launches with more lanes per set, so the longest chain per
 //              lane roughly halves: (a) one SSWU map + isogeny per lane for u0 and u1, the
@@ -138,6 +141,81 @@ __device__ __forceinline__ void pk_bits_slot(bool act, uint32_t s, uint32_t l, c
   }
 }
 
+// Span sets (BGV_SLOT_PK_SPAN; bgv_pk_bits.h): one bitfield over several committees.  The same
+// walk over the span's whole term list: lane l of a team of T takes the terms of rank l, l + T,
+// ..., so its number of additions is ceil((M - l) / T) however the bits fall across the
+// committees.  The member terms come first, record by record -- every lane reads the same record
+// at a time, the key through the record's committee, negated where that committee is on the
+// complement side, and gathered one addition ahead of its use -- then the totals of the
+// complement committees, which are Jacobian and take jac_add.  All additions are the complete
+// ones, so cancelling members, an infinity total and an infinity result take no special case.
+__device__ __forceinline__ g1_aff pk_span_key(uint32_t meta, uint32_t pos, const bgv_dcommittee* __restrict__ dir,
+                                              const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache) {
+  g1_aff a = cache[pool[dir[pkb_meta_handle(meta)].off + pos]];
+  if (pkb_meta_complement(meta)) a.y = fp_neg(a.y);
+  return a;
+}
+template <int T>
+__device__ __forceinline__ g1_jac pk_span_sum(bool act, uint32_t l, const uint32_t* __restrict__ run,
+                                              const bgv_dcommittee* __restrict__ dir,
+                                              const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache) {
+  g1_jac acc = jac_infinity<fp_t>();
+  if (act) {
+    const uint32_t nrec = run[0], ncomp = run[1];
+    const uint32_t* tot = run + PKB_SPAN_HEAD;
+    const uint32_t* recs = tot + ncomp;
+    pkb_span_cursor c = pkb_span_begin(l);
+    uint32_t meta, pos;
+    if (pkb_span_next(c, recs, nrec, T, &meta, &pos)) {
+      acc = jac_from_aff(pk_span_key(meta, pos, dir, pool, cache));
+      bool have = pkb_span_next(c, recs, nrec, T, &meta, &pos);
+      g1_aff cur = {acc.x, acc.y};  // never added unless replaced
+      if (have) cur = pk_span_key(meta, pos, dir, pool, cache);
+      while (have) {
+        const bool hn = pkb_span_next(c, recs, nrec, T, &meta, &pos);
+        g1_aff nxt = cur;
+        if (hn) nxt = pk_span_key(meta, pos, dir, pool, cache);
+        acc = jac_add_aff(acc, cur);
+        cur = nxt;
+        have = hn;
+      }
+    }
+    // the walk ended at c.base = the number of member terms: the lane's totals
+    uint32_t t = c.want - c.base;
+    if (t < ncomp) {
+      g1_jac cur = *reinterpret_cast<const g1_jac*>(dir[tot[t]].total);
+      for (t += T; t < ncomp; t += T) {
+        const g1_jac nxt = *reinterpret_cast<const g1_jac*>(dir[tot[t]].total);
+        acc = jac_add(acc, cur);
+        cur = nxt;
+      }
+      acc = jac_add(acc, cur);
+    }
+  }
+  if constexpr (T == 64) {
+    acc = jac_add(acc, point_xor<32>(acc));
+    acc = jac_add(acc, point_xor<16>(acc));
+  }
+  acc = jac_add(acc, point_xor<8>(acc));
+  acc = jac_add(acc, point_xor<4>(acc));
+  acc = jac_add(acc, point_xor<2>(acc));
+  acc = jac_add(acc, point_xor<1>(acc));
+  return acc;
+}
+
+// pk_agg[s] of span slot s on a 16-lane team (team true: four slots per block, lane % 16 of
+// team lane / 16) or on the whole wave; act false: an idle team.  Out of line: the kernels that
+// call it keep the code and the registers of their own bodies.
+__device__ __noinline__ void pk_span_slot(bool team, bool act, uint32_t s, const bgv_dslot* __restrict__ slots,
+                                          const uint32_t* __restrict__ pk_idx, const bgv_dcommittee* __restrict__ dir,
+                                          const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache,
+                                          g1_jac* __restrict__ pk_agg, bool writer) {
+  const uint32_t* run = act ? pk_idx + slots[s].pk_off : nullptr;
+  const g1_jac acc = team ? pk_span_sum<16>(act, threadIdx.x % 16, run, dir, pool, cache)
+                          : pk_span_sum<64>(act, threadIdx.x, run, dir, pool, cache);
+  if (act && writer) pk_agg[s] = acc;
+}
+
 extern "C" {
 
 // Pubkey aggregation of many-key sets as a wavefront tree (one wave per slot): lane l
@@ -253,12 +331,38 @@ __device__ __noinline__ void pk_bits_one(const bgv_dslot* __restrict__ slots, ui
                                             const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache,
                                             g1_jac* __restrict__ pk_agg) {
   const bgv_dslot& d = slots[s];
-  if ((d.flags & BGV_SLOT_PAD) || !(d.flags & BGV_SLOT_PK_COMMITTEE)) return;  // uniform over the block
+  // uniform over the block; a span slot's sum is in pk_agg already (k_pk_agg_span runs ahead of k_prep_wide)
+  if ((d.flags & (BGV_SLOT_PAD | BGV_SLOT_PK_SPAN)) || !(d.flags & BGV_SLOT_PK_COMMITTEE)) return;
   const uint32_t n = dir[pk_idx[d.pk_off]].n;
   if (pkb_terms(n, d.n_pk, (d.flags & BGV_SLOT_PK_COMPLEMENT) != 0) < BGV_PK_ONE_WAVE_MIN)
     pk_bits_slot<16>(true, s, threadIdx.x % 16, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
   else
     pk_bits_slot<64>(true, s, threadIdx.x, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
+}
+
+// k_pk_agg_bits for the batch's span slots (span: nteam of them on 16-lane teams, four per
+// block, then nwave on a wave each), with the multi-committee body.  A kernel of its own, so
+// k_pk_agg_bits keeps its code and registers; launched only when a batch holds span slots.
+// one != 0 (ahead of k_prep_wide, where nothing else waits for a SIMD): a block per slot of the
+// list, and the shorter chain decides as in pk_bits_one -- a 16-lane team (the four teams of
+// the block repeat each other) below BGV_PK_ONE_WAVE_MIN terms, the whole wave from there on.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BGV_WPE_BITS, BGV_WPE_BITS)))
+k_pk_agg_span(const bgv_dslot* __restrict__ slots, const uint32_t* __restrict__ span, uint32_t nteam, uint32_t nwave,
+              uint32_t one, const uint32_t* __restrict__ pk_idx, const bgv_dcommittee* __restrict__ dir,
+              const uint32_t* __restrict__ pool, const g1_aff* __restrict__ cache, g1_jac* __restrict__ pk_agg) {
+  if (one) {
+    const bool act = blockIdx.x < nteam + nwave;
+    const uint32_t s = act ? span[blockIdx.x] : 0u;
+    const bool team = act && pk_idx[slots[s].pk_off + 2] < BGV_PK_ONE_WAVE_MIN;
+    pk_span_slot(team, act, s, slots, pk_idx, dir, pool, cache, pk_agg, threadIdx.x == 0);
+    return;
+  }
+  const uint32_t nb_team = (nteam + 3) / 4;
+  const bool team = blockIdx.x < nb_team;
+  const uint32_t q = team ? blockIdx.x * 4 + threadIdx.x / 16 : nteam + (blockIdx.x - nb_team);
+  const bool act = q < (team ? nteam : nteam + nwave);
+  pk_span_slot(team, act, act ? span[q] : 0u, slots, pk_idx, dir, pool, cache, pk_agg,
+               (team ? threadIdx.x % 16 : threadIdx.x) == 0);
 }
 
 // The pubkey sums of the committees listed in handles (one wave each) into their directory
@@ -548,12 +652,19 @@ hipError_t bgv_launch_prep(const bgv_dev_batch& b, const bgv_streams& s) {
   // k_pk_agg only when some set is large enough; otherwise k_prep sums serially (null pk_agg)
   const bool tree = b.max_npk >= BGV_PK_TREE_MIN;
   const uint32_t ncom = b.ncom_team + b.ncom_wave;  // committee-bitfield slots: their sums are in pk_agg too
-  const bool agg = tree || ncom > 0;
+  const uint32_t nspan = b.nspan_team + b.nspan_wave;  // span slots: the same, from k_pk_agg_span
+  const bool agg = tree || ncom > 0 || nspan > 0;
   const bool wide = bgv_use_latency(b, n + b.ngroups) && n <= BGV_PREP_WIDE_MAX;
   if (wide) {
     const g1_aff* cache = reinterpret_cast<const g1_aff*>(b.cache_opaque);
     const hipError_t e = bgv_launch_prep_wave(b, s.main);
     if (e != hipSuccess) return e;
+    // Span slots first, in a launch of their own: their body inside plane 3 (as pk_bits_one is)
+    // grew k_prep_wide's scratch frame from 5,632 to 6,192 B per lane for every call.  A block per
+    // set, as plane 3 has.
+    if (nspan)
+      hipLaunchKernelGGL(k_pk_agg_span, dim3(nspan), dim3(64), 0, s.main, b.slots, b.span, b.nspan_team, b.nspan_wave,
+                         1u, b.pk_idx, b.com_dir, b.com_pool, cache, b.pk_agg);
     hipLaunchKernelGGL(k_prep_wide, dim3(n, 4), dim3(64), 0, s.main, b.slots, n, b.h, b.f, b.rsig, b.sig_status,
                        b.pk_idx, cache, b.pk_bytes, b.rpk, b.pk_status, agg ? b.pk_agg : nullptr, b.com_dir, b.com_pool);
     BGV_MARK(1);
@@ -562,6 +673,10 @@ hipError_t bgv_launch_prep(const bgv_dev_batch& b, const bgv_streams& s) {
   if (ncom)
     hipLaunchKernelGGL(k_pk_agg_bits, dim3(nblk(b.ncom_team, 4) + b.ncom_wave), dim3(64), 0, s.main, b.slots, b.com,
                        b.ncom_team, b.ncom_wave, b.pk_idx, b.com_dir, b.com_pool,
+                       reinterpret_cast<const g1_aff*>(b.cache_opaque), b.pk_agg);
+  if (nspan)
+    hipLaunchKernelGGL(k_pk_agg_span, dim3(nblk(b.nspan_team, 4) + b.nspan_wave), dim3(64), 0, s.main, b.slots, b.span,
+                       b.nspan_team, b.nspan_wave, 0u, b.pk_idx, b.com_dir, b.com_pool,
                        reinterpret_cast<const g1_aff*>(b.cache_opaque), b.pk_agg);
   if (tree)
     hipLaunchKernelGGL(k_pk_agg16, dim3(nblk(n, 4)), dim3(64), 0, s.main, b.slots, n, b.pk_idx,
@@ -598,14 +713,19 @@ hipError_t bgv_launch_aggregate(const bgv_dslot* slot, const uint32_t* idx, uint
 // The aggregate of one committee slot through k_pk_agg_bits.  slot: one device bgv_dslot
 // {PK_COMMITTEE [| PK_COMPLEMENT], n_pk = bits set, pk_off = 0}; idx: the handle, then the bit
 // words; list: one zero word (the slot's id); team: the chosen side has at most
-// BGV_PK_TEAM_MAX terms; agg: one g1_jac of scratch
+// BGV_PK_TEAM_MAX terms; span: a span slot {PK_COMMITTEE | PK_SPAN}, idx its run (k_pk_agg_span);
+// agg: one g1_jac of scratch
 hipError_t bgv_launch_aggregate_bits(const bgv_dslot* slot, const uint32_t* idx, const uint32_t* list, bool team,
-                                     const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
+                                     bool span, const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
                                      void* agg, uint8_t* out96, hipStream_t st) {
   const g1_aff* c = reinterpret_cast<const g1_aff*>(cache);
   g1_jac* a = reinterpret_cast<g1_jac*>(agg);
-  hipLaunchKernelGGL(k_pk_agg_bits, dim3(1), dim3(64), 0, st, slot, list, team ? 1u : 0u, team ? 0u : 1u, idx, dir, pool,
-                     c, a);
+  if (span)
+    hipLaunchKernelGGL(k_pk_agg_span, dim3(1), dim3(64), 0, st, slot, list, team ? 1u : 0u, team ? 0u : 1u, 0u, idx,
+                       dir, pool, c, a);
+  else
+    hipLaunchKernelGGL(k_pk_agg_bits, dim3(1), dim3(64), 0, st, slot, list, team ? 1u : 0u, team ? 0u : 1u, idx, dir,
+                       pool, c, a);
   hipLaunchKernelGGL(k_pk_sum_out, dim3(1), dim3(64), 0, st, slot, idx, c, a, out96);
   return hipGetLastError();
 }

@@ -44,6 +44,9 @@ struct bgv_dev_batch {
   // index pool (bgv_committee_put)
   const uint32_t* com;
   uint32_t ncom_team, ncom_wave;
+  // the span slots (BGV_SLOT_PK_SPAN) the same way, after them in the same array, for k_pk_agg_span
+  const uint32_t* span;
+  uint32_t nspan_team, nspan_wave;
   const bgv_dcommittee* com_dir;
   const uint32_t* com_pool;
   // carved per-slot / per-group scratch
@@ -119,7 +122,7 @@ hipError_t bgv_launch_cache_put(const uint8_t* keys, uint32_t n, int fmt, bgv_ca
 hipError_t bgv_launch_aggregate(const bgv_dslot* slot, const uint32_t* idx, uint32_t n, const bgv_cache_entry* cache,
                                 void* agg, uint8_t* out96, hipStream_t st);
 hipError_t bgv_launch_aggregate_bits(const bgv_dslot* slot, const uint32_t* idx, const uint32_t* list, bool team,
-                                     const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
+                                     bool span, const bgv_dcommittee* dir, const uint32_t* pool, const bgv_cache_entry* cache,
                                      void* agg, uint8_t* out96, hipStream_t st);
 // the pubkey sums of the committees in handles into their directory entries
 hipError_t bgv_launch_committee_totals(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, const uint32_t* pool,

@@ -22,6 +22,12 @@ enum {
   // with BGV_SLOT_PK_COMMITTEE: the members whose bit is CLEAR are summed and subtracted from the
   // committee's total (fewer additions when more than half take part)
   BGV_SLOT_PK_COMPLEMENT = 16u,
+  // with BGV_SLOT_PK_COMMITTEE: one bitfield laid over SEVERAL committees (bgv_verify_spans).  At
+  // pk_off the run bgv_pk_bits.h describes (pkb_span_build): the number of selection records and
+  // of complement committees, those committees' handles, then per non-empty selection word a
+  // record of two words; n_pk counts the set bits.  k_pk_agg_span sums the slot into pk_agg.
+  // BGV_SLOT_PK_COMPLEMENT is not used: every committee of the span takes its own side
+  BGV_SLOT_PK_SPAN = 32u,
 };
 
 // Per-slot input record (160 B, 16-B aligned).

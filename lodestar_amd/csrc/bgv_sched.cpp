@@ -209,12 +209,11 @@ static void call_fail(Call* call, int rc) {
 // job goes to the device, else its verdict (empty job, empty aggregate, an index that is not
 // in the cache -- the first such set in set order).  -BGV_E_ARG for a malformed set record.
 // The caller holds cache_mu (shared).
-// A committee set (pkbits[i].committee != BGV_NO_COMMITTEE) is checked against the live
-// committee of its id (committee_set_check); with a call, what the layout needs of it goes to
+// A committee set (pk.is_com(i)) is checked against the live committee of its id
+// (committee_set_check), a span set against every committee of its list (span_set_check); with a call, what the layout needs of it goes to
 // call->setcom and the call takes a reference to the committee.  The caller holds com_mu (shared)
 // when pkbits is given.
-int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code, const bgv_pkbits* pkbits,
-                  Call* call) {
+int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code, PkForm pk, Call* call) {
   *code = 2;
   if (jb.n_sets == 0) {
     *code = -BGV_E_EMPTY_SET;
@@ -222,8 +221,28 @@ int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* c
   }
   for (uint32_t k = 0; k < jb.n_sets && *code == 2; ++k) {
     const bgv_set& s = sets[jb.first_set + k];
-    if (pkbits && pkbits[jb.first_set + k].committee != BGV_NO_COMMITTEE) {
-      const bgv_pkbits& pb = pkbits[jb.first_set + k];
+    if (pk.spans && pk.is_com(jb.first_set + k)) {
+      const bgv_pkspan& sp = pk.spans[jb.first_set + k];
+      if (!s.msg || (!s.sig && s.sig_len) || !sp.committees || (!sp.bits && sp.n_bits)) return -BGV_E_ARG;
+      std::vector<std::shared_ptr<CommitteeRec>> recs;  // the listed committees, once each
+      SetCommittee sc;
+      *code = span_set_check(
+          [&](uint32_t id, CommitteeInfo* ci) {
+            const auto it = c->committees.find(id);
+            if (it == c->committees.end()) return false;
+            *ci = CommitteeInfo{it->second->handle, (uint32_t)it->second->idx.size(), it->second->bad};
+            if (call && (recs.empty() || recs.back() != it->second)) recs.push_back(it->second);
+            return true;
+          },
+          sp, &sc);
+      if (*code == 2 && call) {
+        call->setcom[jb.first_set + k] = std::move(sc);
+        call->com_refs.insert(call->com_refs.end(), recs.begin(), recs.end());
+      }
+      continue;
+    }
+    if (pk.bits && pk.is_com(jb.first_set + k)) {
+      const bgv_pkbits& pb = pk.bits[jb.first_set + k];
       if (!s.msg || (!s.sig && s.sig_len) || (!pb.bits && pb.n_bits)) return -BGV_E_ARG;
       const auto it = c->committees.find(pb.committee);
       const CommitteeRec* rec = it != c->committees.end() ? it->second.get() : nullptr;
@@ -263,7 +282,7 @@ static void advise_huge(void* p, size_t bytes) {
 // host-side checks and layout, on the caller's thread
 static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
                        int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user, int dev = -1,
-                       const bgv_pkbits* pkbits = nullptr) {
+                       PkForm pkbits = PkForm()) {
   call->t0 = std::chrono::steady_clock::now();
   call->dev = dev;
   if (c->closed) return -BGV_E_CLOSED;
@@ -279,7 +298,6 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
   call->done = done;
   call->user = user;
   call->code.assign(njobs, 2);
-  call->pkbits = pkbits;
   if (pkbits) call->setcom.assign(nsets, SetCommittee{});
   {
     std::shared_lock<std::shared_mutex> clk(c->cache_mu);
@@ -290,14 +308,16 @@ static int call_submit(bgv_ctx* c, Call* call, const bgv_job* jobs, size_t njobs
       if (host_job_code(c, jobs[j], sets, &call->code[j], pkbits, call) != BGV_OK) return -BGV_E_ARG;
     }
   }
-  const auto is_com = [pkbits](size_t i) { return pkbits && pkbits[i].committee != BGV_NO_COMMITTEE; };
+  const auto is_com = [pkbits](size_t i) { return pkbits.is_com(i); };
   // pass-1 layout (bgv_host_layout.h)
   Layout& L = call->L;
   {
     size_t npk = 0;
     for (size_t i = 0; i < nsets; ++i)
-      if (is_com(i))
-        npk += 1 + pkb_nwords(call->setcom[i].n);  // the handle and the bit words (a refused set: n = 0)
+      if (is_com(i))  // the handle and the bit words (a refused set: n = 0); a span's run has its header
+                      // and at most two words per bit word and three per committee
+        npk += PKB_SPAN_HEAD + (call->setcom[i].parts.empty() ? 1 : 2) * pkb_nwords(call->setcom[i].n) +
+               3 * call->setcom[i].parts.size();
       else if (sets[i].pk_indices)
         npk += sets[i].n_pk;
     const size_t cap = nsets + nsets / 8 + BGV_WAVE;  // with room for the groups' padding
@@ -348,7 +368,7 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   double t_merge = 0, t_tok = 0, t_sets = 0, t_pass1 = 0, t_post = 0;
   // merge the calls' layouts
   uint32_t nslots = 0, ngroups = 0;
-  size_t nidx = 0, npkb = 0, nuniq = 0, ncom_team = 0, ncom_wave = 0;
+  size_t nidx = 0, npkb = 0, nuniq = 0, ncom_team = 0, ncom_wave = 0, nspan_team = 0, nspan_wave = 0;
   bool any_uniform = false;
   for (Call* call : calls) {
     call->slot_base = nslots;
@@ -359,9 +379,12 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
     nuniq += call->L.uniq.size();
     ncom_team += call->L.com_team.size();
     ncom_wave += call->L.com_wave.size();
+    nspan_team += call->L.span_team.size();
+    nspan_wave += call->L.span_wave.size();
     for (char u : call->L.group_uniform) any_uniform = any_uniform || u;
   }
-  const size_t ncom = ncom_team + ncom_wave, nlist = nuniq + ncom;  // the lists after the indices
+  const size_t ncom = ncom_team + ncom_wave, nspan = nspan_team + nspan_wave;
+  const size_t nlist = nuniq + ncom + nspan;  // the lists after the indices
   const bool bulk = nslots + ngroups > bgv_fold_pairs_max();
   // uniform groups (BGV_GROUP_UNIFORM): bulk batches (the two-phase Miller stage)
   const bool uniform = uniform_enabled() && any_uniform && bulk;
@@ -423,6 +446,10 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
       for (uint32_t v : call->L.com_team) *u++ = v + call->slot_base;
     for (Call* call : calls)
       for (uint32_t v : call->L.com_wave) *u++ = v + call->slot_base;
+    for (Call* call : calls)
+      for (uint32_t v : call->L.span_team) *u++ = v + call->slot_base;
+    for (Call* call : calls)
+      for (uint32_t v : call->L.span_wave) *u++ = v + call->slot_base;
   }
   std::vector<uint64_t> sc(nslots);
   fill_scalars(c, sc.data(), nslots);
@@ -451,6 +478,9 @@ static int run_pass1(bgv_ctx* c, Device& d, Exec& x, std::vector<Call*>& calls, 
   b.com = x.d_idx + nidx + nuniq;
   b.ncom_team = (uint32_t)ncom_team;
   b.ncom_wave = (uint32_t)ncom_wave;
+  b.span = b.com + ncom;
+  b.nspan_team = (uint32_t)nspan_team;
+  b.nspan_wave = (uint32_t)nspan_wave;
   if (int lrc = exec_reserve_lines(x, b)) return lrc;
   bgv_streams S{x.main, prof ? x.kev : nullptr};
   int32_t *ss = x.h_ss.p, *ps = x.h_ps.p, *verdict = x.h_verdict.p;
@@ -987,7 +1017,7 @@ int bgv_set_rng_seed(bgv_ctx* c, uint64_t seed) {
 // ---------------------------------------------------------------------------
 // One job's sets -> its Fp12 Miller-loop product and status codes on device dev (-1: any).
 static int partial_submit(bgv_ctx* c, Call* call, const bgv_set* sets, size_t nsets, uint8_t* out576,
-                          int32_t* out_codes, int dev, const bgv_pkbits* pkbits = nullptr) {
+                          int32_t* out_codes, int dev, PkForm pkbits = PkForm()) {
   out_codes[0] = out_codes[1] = 0;
   fp12_one_bytes(out576);
   call->partial_out = out576;
@@ -1043,7 +1073,7 @@ static void split_leave(bgv_ctx* c) {
 }
 
 static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
-                        const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats) {
+                        PkForm pkbits, int mode, int32_t* out, bgv_stats* stats) {
   const auto t0 = std::chrono::steady_clock::now();
   const size_t K = c->devs.size(), big = split_min_sets(c);
   struct Shard {  // one run of a big job on one device
@@ -1117,7 +1147,7 @@ static int verify_split(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv
       auto sh = std::make_unique<Shard>();
       sh->job = j;
       sh->rc = partial_submit(c, &sh->call, sets + jobs[j].first_set + lo, hi - lo, sh->part, sh->codes, (int)d,
-                              pkbits ? pkbits + jobs[j].first_set + lo : nullptr);
+                              pkbits.from(jobs[j].first_set + lo));
       if (sh->rc != BGV_OK && rc == BGV_OK) rc = sh->rc;
       shards.push_back(std::move(sh));
     }
@@ -1183,18 +1213,24 @@ int bgv_set_split(bgv_ctx* c, uint32_t min_sets) {
   return BGV_OK;
 }
 
+static int verify_sync(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, PkForm pkbits,
+                       int mode, int32_t* out, bgv_stats* stats);
+static int verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                        PkForm pkbits, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user);
+
 int bgv_verify(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
                int32_t* out, bgv_stats* stats) {
-  return bgv_verify_bits(c, jobs, njobs, sets, nsets, nullptr, mode, out, stats);
+  return verify_sync(c, jobs, njobs, sets, nsets, PkForm(), mode, out, stats);
 }
 
 int bgv_verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, int mode,
                      int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user) {
-  return bgv_verify_bits_async(c, jobs, njobs, sets, nsets, nullptr, mode, out, stats, done, user);
+  return verify_async(c, jobs, njobs, sets, nsets, PkForm(), mode, out, stats, done, user);
 }
 
-int bgv_verify_bits(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
-                    const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats) {
+// pkbits: how the sets name their pubkeys (bgv_verify, bgv_verify_bits, bgv_verify_spans)
+static int verify_sync(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets, PkForm pkbits,
+                       int mode, int32_t* out, bgv_stats* stats) {
   if (!c) return -BGV_E_ARG;
   if (split_wanted(c, nsets)) {
     if (c->closed) return -BGV_E_CLOSED;
@@ -1216,9 +1252,8 @@ int bgv_verify_bits(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set
   return rc;
 }
 
-int bgv_verify_bits_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
-                          const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done,
-                          void* user) {
+static int verify_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                        PkForm pkbits, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done, void* user) {
   if (!c) return -BGV_E_ARG;
   if (split_wanted(c, nsets)) {
     // a split call waits for its pieces and combines them: on a thread of its own (big calls
@@ -1239,6 +1274,28 @@ int bgv_verify_bits_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const b
   int rc = call_submit(c, call, jobs, njobs, sets, nsets, mode, out, stats, done, user, -1, pkbits);
   if (rc != BGV_OK) delete call;
   return rc;
+}
+
+int bgv_verify_bits(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                    const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats) {
+  return verify_sync(c, jobs, njobs, sets, nsets, PkForm(pkbits), mode, out, stats);
+}
+
+int bgv_verify_bits_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                          const bgv_pkbits* pkbits, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done,
+                          void* user) {
+  return verify_async(c, jobs, njobs, sets, nsets, PkForm(pkbits), mode, out, stats, done, user);
+}
+
+int bgv_verify_spans(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                     const bgv_pkspan* spans, int mode, int32_t* out, bgv_stats* stats) {
+  return verify_sync(c, jobs, njobs, sets, nsets, PkForm(spans), mode, out, stats);
+}
+
+int bgv_verify_spans_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                           const bgv_pkspan* spans, int mode, int32_t* out, bgv_stats* stats, bgv_done_fn done,
+                           void* user) {
+  return verify_async(c, jobs, njobs, sets, nsets, PkForm(spans), mode, out, stats, done, user);
 }
 
 int bgv_verify_partial(bgv_ctx* c, const bgv_set* sets, size_t nsets, uint8_t out576[576], int32_t out_codes[2]) {

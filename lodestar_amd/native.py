@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "bgv_committee_put", "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
     "bgv_aggregate_committee_bits", "bgv_shuffling_put", "bgv_committee_drop_range",
     "bgv_proposers", "bgv_sync_committee_put",
+    "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
 ]
 
 
@@ -64,6 +65,11 @@ class BgvSet(ctypes.Structure):
 
 class BgvPkBits(ctypes.Structure):
     _fields_ = [("committee", ctypes.c_uint32), ("n_bits", ctypes.c_uint32), ("bits", ctypes.c_void_p)]
+
+
+class BgvPkSpan(ctypes.Structure):
+    _fields_ = [("committees", ctypes.c_void_p), ("n_committees", ctypes.c_uint32), ("n_bits", ctypes.c_uint32),
+                ("bits", ctypes.c_void_p)]
 
 
 class BgvJob(ctypes.Structure):
@@ -134,12 +140,16 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_committee_drop_range": ([P, U32, U32], ctypes.c_int),
             "bgv_proposers": ([P, P, U32, P, SZ, P, SZ, U32, U32, P], ctypes.c_int),
             "bgv_sync_committee_put": ([P, U32, P, P, SZ, P, SZ, U32, U32, U32, P, P], ctypes.c_int),
+            "bgv_verify_spans": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P], ctypes.c_int),
+            "bgv_verify_spans_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, DONE_FN, P], ctypes.c_int),
+            "bgv_aggregate_span": ([P, P, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
                         "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
                         "bgv_aggregate_committee_bits", "bgv_shuffling_put",
-                        "bgv_committee_drop_range", "bgv_proposers", "bgv_sync_committee_put") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_committee_drop_range", "bgv_proposers", "bgv_sync_committee_put",
+                        "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -311,6 +321,17 @@ class Context:
         _check(self.lib.bgv_aggregate_committee_bits(self._h, committee_id, _buf(bits), n_bits, out))
         return out.raw
 
+    def aggregate_span(self, committees: Sequence[int], bits: bytes, n_bits: int) -> bytes:
+        """The aggregate of the members one bitfield selects over the listed committees (committee
+        c owns the bits from the sum of the lengths before it on), 96 B uncompressed, through the
+        verify path's kernel (bgv_aggregate_span)."""
+        ids = (ctypes.c_uint32 * max(1, len(committees)))(*committees)
+        b = _buf(bits)
+        span = BgvPkSpan(ctypes.addressof(ids), len(committees), n_bits, ctypes.addressof(b))
+        out = ctypes.create_string_buffer(96)
+        _check(self.lib.bgv_aggregate_span(self._h, ctypes.byref(span), out))
+        return out.raw
+
     def keygen(self, sks: bytes, cache_first: int = -1, want_pubkeys: bool = True) -> bytes:
         n = len(sks) // 32
         out = ctypes.create_string_buffer(48 * n) if want_pubkeys else None
@@ -423,7 +444,10 @@ class Context:
         njobs = len(packed.jobs_in)
         out = (ctypes.c_int32 * max(1, njobs))()
         st = ctypes.byref(stats) if stats is not None else None
-        if packed.pkbits is not None:  # some set names (committee, bitfield)
+        if packed.spans is not None:  # some set names several committees under one bitfield
+            rc = self.lib.bgv_verify_spans(self._h, packed.jobs, njobs, packed.sets, packed.nsets, packed.spans,
+                                           mode, out, st)
+        elif packed.pkbits is not None:  # some set names (committee, bitfield)
             rc = self.lib.bgv_verify_bits(self._h, packed.jobs, njobs, packed.sets, packed.nsets, packed.pkbits,
                                           mode, out, st)
         else:
@@ -435,13 +459,22 @@ class Context:
 class SetSpec:
     """One ISignatureSet in C-ABI terms: pubkeys by cache index, as 96-B bytes, or as the members
     of a device-resident committee (Context.committee_put) selected by an SSZ bitfield of n_bits
-    bits (member k takes part iff (bits[k >> 3] >> (k & 7)) & 1)."""
+    bits (member k takes part iff (bits[k >> 3] >> (k & 7)) & 1).  committees=[ids] lays the one
+    bitfield over several committees, concatenated in list order (bgv_pkspan); a list of one id is
+    committee=id."""
 
-    __slots__ = ("pk_indices", "pk_bytes", "msg", "sig", "committee", "bits", "n_bits")
+    __slots__ = ("pk_indices", "pk_bytes", "msg", "sig", "committee", "committees", "bits", "n_bits")
 
     def __init__(self, msg: bytes, sig: bytes, pk_indices: Optional[Sequence[int]] = None,
                  pk_bytes: Optional[Sequence[bytes]] = None, committee: Optional[int] = None,
-                 bits: Optional[bytes] = None, n_bits: Optional[int] = None):
+                 bits: Optional[bytes] = None, n_bits: Optional[int] = None,
+                 committees: Optional[Sequence[int]] = None):
+        if committees is not None:
+            if committee is not None or len(committees) == 0:
+                raise ValueError("committees takes at least one id, and no committee beside it")
+            committees = [int(c) for c in committees]
+            committee = committees[0]  # the checks below; a list of one id is that committee set
+        self.committees = committees if committees is not None and len(committees) > 1 else None
         self.pk_indices = list(pk_indices) if pk_indices is not None else None
         self.pk_bytes = list(pk_bytes) if pk_bytes is not None else None
         self.msg = bytes(msg)
@@ -511,8 +544,11 @@ class PackedCall:
         sarr = (BgvSet * max(1, len(all_sets)))()
         keep = []
         # the bgv_pkbits array beside the sets, only when some set names a committee
-        self.pkbits = None
-        if any(s.committee is not None for s in all_sets):
+        # ... or the bgv_pkspan array, when some set names more than one committee
+        self.pkbits = self.spans = None
+        if any(s.committees is not None for s in all_sets):
+            self.spans = (BgvPkSpan * max(1, len(all_sets)))()  # zeroed: n_committees = 0
+        elif any(s.committee is not None for s in all_sets):
             self.pkbits = (BgvPkBits * max(1, len(all_sets)))()
             for i in range(len(all_sets)):
                 self.pkbits[i].committee = NO_COMMITTEE
@@ -529,9 +565,18 @@ class PackedCall:
             if s.committee is not None:
                 bits = _buf(s.bits)
                 keep.append(bits)
-                self.pkbits[i].committee = s.committee
-                self.pkbits[i].n_bits = s.n_bits
-                self.pkbits[i].bits = ctypes.addressof(bits)
+                if self.spans is not None:
+                    ids = s.committees if s.committees is not None else [s.committee]
+                    arr = (ctypes.c_uint32 * len(ids))(*ids)
+                    keep.append(arr)
+                    self.spans[i].committees = ctypes.addressof(arr)
+                    self.spans[i].n_committees = len(ids)
+                    self.spans[i].n_bits = s.n_bits
+                    self.spans[i].bits = ctypes.addressof(bits)
+                else:
+                    self.pkbits[i].committee = s.committee
+                    self.pkbits[i].n_bits = s.n_bits
+                    self.pkbits[i].bits = ctypes.addressof(bits)
             elif s.pk_indices is not None:
                 idx = (ctypes.c_uint32 * max(1, len(s.pk_indices)))(*s.pk_indices)
                 keep.append(idx)

@@ -37,8 +37,9 @@ const MAX_BUFFER_WAIT_MS = 1;
 
 // committee: not in the reference -- an aggregate as the beacon node holds it before
 // bits.intersectValues(committeeIndices): a committee stored on the device (committeePut) and
-// the participation bitfield
-const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee"};
+// the participation bitfield; committees: one bitfield over several such committees in order
+// (an attestation since EIP-7549: committee_bits -> ids, aggregation_bits)
+const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee", committees: "committees"};
 const PUBKEY_RUN = 8192;
 const NO_PROPOSER = 0xffffffff; // BGV_NO_PROPOSER
 // include/blsgpu.h: BGV_BLST_* decode statuses are 1..19 (library codes start at 20)
@@ -86,7 +87,8 @@ function getAggregatedPubkeysCount(sets) {
   let n = 0;
   for (const s of sets) {
     if (s.type === SignatureSetType.aggregate) n += s.pubkeys.length;
-    else if (s.type === SignatureSetType.committee) n += countBits(committeeBits(s).bits);
+    else if (s.type === SignatureSetType.committee || s.type === SignatureSetType.committees)
+      n += countBits(committeeBits(s).bits);
   }
   return n;
 }
@@ -122,6 +124,10 @@ function toNativeSet(s) {
   if (s.type === SignatureSetType.committee) {
     const {bits, nBits} = committeeBits(s);
     return {committee: s.committee, bits, nBits, msg: s.signingRoot, sig: s.signature};
+  }
+  if (s.type === SignatureSetType.committees) {
+    const {bits, nBits} = committeeBits(s);
+    return {committees: Uint32Array.from(s.committees), bits, nBits, msg: s.signingRoot, sig: s.signature};
   }
   let pks;
   if (s.type === SignatureSetType.single) pks = [s.pubkey];

@@ -110,6 +110,8 @@ typedef struct {
   bgv_set* sets;
   bgv_pkbits* pkbits; /* beside sets; handed to the library only when a set names a committee */
   int any_committee;
+  bgv_pkspan* spans; /* beside sets; handed to the library instead when a set names several committees */
+  int any_span;
   size_t nsets;
   int mode;
   int32_t* codes;
@@ -771,6 +773,7 @@ static void free_req(napi_env env, verify_req* r) {
   free(r->jobs);
   free(r->sets);
   free(r->pkbits);
+  free(r->spans);
   free(r->codes);
   free(r);
 }
@@ -823,6 +826,8 @@ static void verify_call_js(napi_env env, napi_value js_cb, void* context, void* 
     free(r->refs);
     free(r->jobs);
     free(r->sets);
+    free(r->pkbits);
+    free(r->spans);
     free(r->codes);
     free(r);
   }
@@ -888,6 +893,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   size_t cap = 64;
   r->sets = (bgv_set*)calloc(cap, sizeof(bgv_set));
   r->pkbits = (bgv_pkbits*)calloc(cap, sizeof(bgv_pkbits));
+  r->spans = (bgv_pkspan*)calloc(cap, sizeof(bgv_pkspan));
   size_t refcap = 256;
   r->refs = (napi_ref*)calloc(refcap, sizeof(napi_ref));
   for (uint32_t j = 0; j < njobs; ++j) {
@@ -907,6 +913,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
         cap *= 2;
         r->sets = (bgv_set*)realloc(r->sets, cap * sizeof(bgv_set));
         r->pkbits = (bgv_pkbits*)realloc(r->pkbits, cap * sizeof(bgv_pkbits));
+        r->spans = (bgv_pkspan*)realloc(r->spans, cap * sizeof(bgv_pkspan));
       }
       if (r->nrefs + 4 > refcap) {
         refcap *= 2;
@@ -916,9 +923,12 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
       napi_get_element(env, sets, k, &s);
       /* pkIndices (validator indices into the device cache), pkBytes (n x 96-B uncompressed), or
        * committee + bits + nBits (the members of a committee stored with committeePut whose bit is
-       * set, SSZ bit order: bgv_pkbits) */
-      bool by_index = false, by_committee = false;
+       * set, SSZ bit order: bgv_pkbits), or committees (a Uint32Array of ids) + bits + nBits (one
+       * bitfield over those committees in order: bgv_pkspan) */
+      bool by_index = false, by_committee = false, by_span = false;
+      napi_has_named_property(env, s, "committees", &by_span);
       napi_has_named_property(env, s, "committee", &by_committee);
+      by_committee = by_committee || by_span;
       napi_has_named_property(env, s, "pkIndices", &by_index);
       napi_get_named_property(env, s, by_committee ? "bits" : by_index ? "pkIndices" : "pkBytes", &pk);
       napi_get_named_property(env, s, "msg", &msg);
@@ -927,6 +937,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
       pb->committee = BGV_NO_COMMITTEE;
       pb->n_bits = 0;
       pb->bits = NULL;
+      memset(&r->spans[r->nsets], 0, sizeof(bgv_pkspan));
       bgv_set* st = &r->sets[r->nsets++];
       memset(st, 0, sizeof(*st));
       uint8_t *pkd, *md, *sd;
@@ -936,7 +947,30 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
         free_req(env, r);
         return throw_code(env, -BGV_E_ARG);
       }
-      if (by_committee) {
+      if (by_span) {
+        napi_value cv, nv;
+        uint8_t* cd;
+        size_t cl;
+        uint32_t nbits = 0;
+        napi_typedarray_type tt = napi_uint8_array;
+        bool is_ta = false;
+        napi_get_named_property(env, s, "committees", &cv);
+        napi_get_named_property(env, s, "nBits", &nv);
+        napi_is_typedarray(env, cv, &is_ta);
+        if (is_ta) napi_get_typedarray_info(env, cv, &tt, NULL, NULL, NULL, NULL);
+        if (!is_ta || tt != napi_uint32_array || get_bytes(env, cv, &cd, &cl) || cl == 0 ||
+            napi_get_value_uint32(env, nv, &nbits) != napi_ok || pkl != ((size_t)nbits + 7) / 8) {
+          free_req(env, r);
+          return throw_code(env, -BGV_E_ARG);
+        }
+        bgv_pkspan* sp = &r->spans[r->nsets - 1];
+        sp->committees = (const uint32_t*)cd;
+        sp->n_committees = (uint32_t)(cl / 4);
+        sp->n_bits = nbits;
+        sp->bits = pkd;
+        r->any_span = 1;
+        napi_create_reference(env, cv, 1, &r->refs[r->nrefs++]);
+      } else if (by_committee) {
         napi_value cv, nv;
         uint32_t cid = 0, nbits = 0;
         napi_get_named_property(env, s, "committee", &cv);
@@ -970,8 +1004,21 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   /* the ctx external stays alive (no finalizer) until this request completes */
   CHECK(env, napi_create_reference(env, argv[0], 1, &r->ctx_ref));
   if (a->inflight++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
-  int rc = bgv_verify_bits_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_committee ? r->pkbits : NULL,
-                                 r->mode, r->codes, &r->stats, verify_done, r);
+  int rc;
+  if (r->any_span) { /* the one-committee sets of the call as spans of one committee */
+    for (size_t i = 0; i < r->nsets; ++i)
+      if (r->pkbits[i].committee != BGV_NO_COMMITTEE) {
+        r->spans[i].committees = &r->pkbits[i].committee;
+        r->spans[i].n_committees = 1;
+        r->spans[i].n_bits = r->pkbits[i].n_bits;
+        r->spans[i].bits = r->pkbits[i].bits;
+      }
+    rc = bgv_verify_spans_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->spans, r->mode, r->codes, &r->stats,
+                                verify_done, r);
+  } else {
+    rc = bgv_verify_bits_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_committee ? r->pkbits : NULL,
+                               r->mode, r->codes, &r->stats, verify_done, r);
+  }
   if (rc) { /* rejected before queueing (closed, bad arguments): settle now */
     r->rc = rc;
     settle(env, r);

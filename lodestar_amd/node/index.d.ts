@@ -22,6 +22,7 @@ export declare const SignatureSetType: {
   readonly single: "single";
   readonly aggregate: "aggregate";
   readonly committee: "committee";
+  readonly committees: "committees";
 };
 export type SignatureSetType = typeof SignatureSetType[keyof typeof SignatureSetType];
 
@@ -54,7 +55,24 @@ export interface ICommitteeSignatureSet {
   signingRoot: Uint8Array;
   signature: Uint8Array;
 }
-export type ISignatureSet = ISingleSignatureSet | IAggregatedSignatureSet | ICommitteeSignatureSet;
+/**
+ * One bitfield over several stored committees, concatenated in list order: committee c owns the
+ * bits from the sum of the lengths before it on (an attestation since EIP-7549: committee_bits
+ * mapped to ids, aggregation_bits).  A repeated id counts its selected members again.
+ */
+export interface ICommitteesSignatureSet {
+  type: "committees";
+  committees: number[];
+  bits: Uint8Array | {uint8Array: Uint8Array; bitLen: number};
+  nBits?: number;
+  signingRoot: Uint8Array;
+  signature: Uint8Array;
+}
+export type ISignatureSet =
+  | ISingleSignatureSet
+  | IAggregatedSignatureSet
+  | ICommitteeSignatureSet
+  | ICommitteesSignatureSet;
 
 export interface BlsGpuVerifierOpts {
   devices?: number[];

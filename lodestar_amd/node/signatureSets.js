@@ -42,7 +42,7 @@ const G2_POINT_AT_INFINITY = (() => {
   b[0] = 0xc0;
   return b;
 })();
-const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee"};
+const SignatureSetType = {single: "single", aggregate: "aggregate", committee: "committee", committees: "committees"};
 
 const ssz = require("./ssz.js");
 
@@ -228,6 +228,23 @@ function getAttestationBitsSignatureSet(state, attestation, committeeId, types) 
   };
 }
 
+/**
+ * An attestation since EIP-7549 without the expansion of get_attesting_indices: committeeIds are
+ * the device ids (BlsGpuVerifier.committeePut / shufflingPut) of the committees its committee_bits
+ * selects, in ascending committee order, and aggregationBits (a BitArray, or bytes) is the one
+ * bitfield laid over them.  The caller computes the signing root (the post-Electra containers
+ * are not restated here).
+ */
+function getAttestationCommitteesBitsSignatureSet(committeeIds, aggregationBits, signingRoot, signature) {
+  return {
+    type: SignatureSetType.committees,
+    committees: Array.from(committeeIds),
+    ...bitsOf(aggregationBits, aggregationBits.bitLen === undefined ? 8 * aggregationBits.length : undefined),
+    signingRoot,
+    signature,
+  };
+}
+
 /** indexedAttestation.ts:23-28 */
 function getIndexedAttestationSignatureSet(state, indexedAttestation, types) {
   return getAttestationWithIndicesSignatureSet(state, indexedAttestation, indexedAttestation.attestingIndices, types);
@@ -368,5 +385,6 @@ module.exports = {
   getVoluntaryExitsSignatureSets,
   getSyncCommitteeSignatureSet,
   getAttestationBitsSignatureSet,
+  getAttestationCommitteesBitsSignatureSet,
   getSyncCommitteeBitsSignatureSet,
 };

@@ -41,6 +41,9 @@ class SignatureSetType(enum.Enum):
     # bits.intersectValues(committeeIndices) (epochContext.ts:620-622) -- a committee kept on
     # the device (native.Context.committee_put) and the participation bitfield
     committee = "committee"
+    # one bitfield over several device-resident committees, concatenated in list order: an
+    # attestation since EIP-7549 (committee_bits -> ids, aggregation_bits)
+    committees = "committees"
 
 
 # A public key is a validator index into the device cache (int) or 96 uncompressed bytes.
@@ -58,6 +61,8 @@ class ISignatureSet:
     # type == committee: the committee's id, the SSZ bitfield (member k takes part iff
     # (bits[k >> 3] >> (k & 7)) & 1) and its length in bits (the committee's size)
     committee: Optional[int] = None
+    # type == committees: the committees' ids in bitfield order; bits and n_bits span them all
+    committees: Optional[List[int]] = None
     bits: Optional[bytes] = None
     n_bits: Optional[int] = None
 
@@ -88,7 +93,8 @@ def chunkify_maximize_chunk_size(arr: Sequence, min_per_chunk: int) -> List[list
 def get_aggregated_pubkeys_count(sets: Sequence[ISignatureSet]) -> int:
     """utils.ts:18-26; a committee set counts the members whose bit is set"""
     return sum(len(s.pubkeys) for s in sets if s.type == SignatureSetType.aggregate) + \
-        sum(bin(b).count("1") for s in sets if s.type == SignatureSetType.committee for b in s.bits)
+        sum(bin(b).count("1") for s in sets
+            if s.type in (SignatureSetType.committee, SignatureSetType.committees) for b in s.bits)
 
 
 def to_set_spec(s: ISignatureSet) -> native.SetSpec:
@@ -96,6 +102,8 @@ def to_set_spec(s: ISignatureSet) -> native.SetSpec:
     aggregation itself happens on the device."""
     if s.type == SignatureSetType.committee:
         return native.SetSpec(s.signing_root, s.signature, committee=s.committee, bits=s.bits, n_bits=s.n_bits)
+    if s.type == SignatureSetType.committees:
+        return native.SetSpec(s.signing_root, s.signature, committees=s.committees, bits=s.bits, n_bits=s.n_bits)
     if s.type == SignatureSetType.single:
         pks = [s.pubkey]
     elif s.type == SignatureSetType.aggregate:
