@@ -26,11 +26,11 @@ static __device__ __noinline__ void task_sig(uint32_t s, const bgv_dslot* __rest
       if (inf) {
         st = BGV_ST_INFINITY;  // skipped in the accumulator, as blst does
       } else {
-        const g2_jac j = jac_from_aff(a);
-        if (!g2_in_subgroup(j))
+        // the decoded point stays affine: mixed additions in [|x|]P and in the table of r * sig
+        if (!g2_in_subgroup_aff(a))
           st = BGV_POINT_NOT_IN_GROUP;
         else
-          rsig[s] = jac_mul_glv(j, d.scalar);  // never infinity: 0 < r < group order
+          rsig[s] = jac_mul_glv_aff(a, d.scalar);  // never infinity: 0 < r < group order
       }
     }
   }
@@ -42,7 +42,7 @@ static __device__ __noinline__ void task_hash(uint32_t s, const bgv_dslot* __res
   if (d.flags & BGV_SLOT_PAD) return;
   uint8_t msg[32];
   for (int i = 0; i < 32; ++i) msg[i] = d.msg[i];
-  h[s] = hash_to_g2(msg, 32);  // stays Jacobian: k_miller adds it with miller_add_jq
+  h[s] = hash_to_g2_sum(msg, 32);  // stays Jacobian: k_miller adds it with miller_add_jq
 }
 
 // Sum of one set's pubkeys (PublicKey.aggregate, chain/bls/utils.ts:5-16): the k_pk_agg

@@ -184,6 +184,19 @@ BGV_NOINLINE jac_t<F> jac_add_aff(const jac_t<F>& p, const aff_t<F>& q) {
   return r;
 }
 
+// The complete mixed addition inlined into its caller (the loops of jac_mul_x_abs_aff and
+// jac_mul_glv_aff keep the accumulator in VGPRs, as with jac_add).  P == Q doubles, P == -Q
+// gives Z3 = (Z1 + H)^2 - Z1Z1 - HH = 0 with H == 0 (infinity, as jac_add's Z3 = ... H), P at
+// infinity gives Q.
+template <class F>
+BGV_CURVE_ATTR jac_t<F> jac_madd(const jac_t<F>& p, const aff_t<F>& q) {
+  bool hz, rz;
+  jac_t<F> r = jac_add_aff_raw(p, q, &hz, &rz);
+  const bool pinf = jac_is_inf(p);
+  if (hz && rz && !pinf) r = jac_dbl(p);  // rare: P == Q
+  return jac_select(pinf, r, jac_from_aff(q));
+}
+
 // Jacobian -> affine; returns false for infinity (out untouched = zeros).
 template <class F>
 BGV_NOINLINE bool jac_to_aff(aff_t<F>* out, const jac_t<F>& p) {
@@ -288,6 +301,20 @@ BGV_NOINLINE jac_t<F> jac_mul_x_abs(const jac_t<F>& p) {
     if ((X >> i) & 1) acc = jac_add(acc, pm[bgv_opaque0()]);
   }
   return jac_t<F>{acc.x, acc.y, acc.z};  // not NRVO: acc would live in the caller's return slot (scratch)
+}
+
+// [|x|]P of an affine P (a decoded signature): jac_mul_x_abs with its five additions mixed.
+template <class F>
+BGV_NOINLINE jac_t<F> jac_mul_x_abs_aff(const aff_t<F>& p) {
+  aff_t<F> pm[1];
+  pm[0] = p;
+  jac_t<F> acc = jac_from_aff(p);
+  const uint64_t X = BGV_X_ABS;
+  BGV_NO_UNROLL for (int i = 62; i >= 0; --i) {
+    acc = jac_dbl(acc);
+    if ((X >> i) & 1) acc = jac_madd(acc, pm[bgv_opaque0()]);
+  }
+  return jac_t<F>{acc.x, acc.y, acc.z};  // not NRVO (see jac_mul_x_abs)
 }
 
 // ---------------------------------------------------------------------------
@@ -417,6 +444,52 @@ BGV_NOINLINE jac_t<F> jac_mul_glv(const jac_t<F>& p, uint64_t k) {
   return jac_t<F>{acc.x, acc.y, acc.z};  // not NRVO (see jac_mul_x_abs)
 }
 
+// E on an affine point
+BGV_HD g1_aff aff_endo_x2(const g1_aff& p) {
+  const fp_t beta = {BGV_BETA_MX2};
+  return g1_aff{fp_mul(p.x, beta), fp_neg(p.y)};
+}
+BGV_HD g2_aff aff_endo_x2(const g2_aff& p) {
+  const fp_t cx = {BGV_PSI2_CX};
+  const fp_t cy = {BGV_PSI2_CY};
+  return g2_aff{fp2_mul_fp(p.x, cx), fp2_mul_fp(p.y, cy)};
+}
+
+// jac_mul_glv of an affine P (a decoded signature): the table loop's one addition site adds P
+// (or E(P) in its last turn) and is mixed, 4 of the 20 additions; the window loop is jac_mul_glv's.
+template <class F>
+BGV_NOINLINE jac_t<F> jac_mul_glv_aff(const aff_t<F>& p, uint64_t k) {
+  constexpr int NT = 8, NWIN = 8;
+  const uint32_t a = (uint32_t)k, b = (uint32_t)(k >> 32);
+  const uint64_t ca = bgv_recode16_carries(a), cb = bgv_recode16_carries(b);
+  aff_t<F> pm[1];
+  pm[0] = p;
+  jac_t<F> tab[NT];
+  tab[0] = jac_from_aff(p);
+  jac_t<F> acc = jac_select(((ca >> 32) & 1u) != 0u, jac_infinity<F>(), tab[0]);
+  BGV_NO_UNROLL for (int i = 1; i <= NT; ++i) {
+    if (i < NT && (i & 1)) {
+      tab[i] = jac_dbl(tab[i >> 1]);
+      continue;
+    }
+    const bool last = i == NT;
+    const jac_t<F> l = last ? acc : tab[i - 1];
+    aff_t<F> r = pm[bgv_opaque0()];
+    if (last) r = aff_endo_x2(r);
+    const jac_t<F> s = jac_madd(l, r);
+    if (last)
+      acc = jac_select(((cb >> 32) & 1u) != 0u, acc, s);
+    else
+      tab[i] = s;
+  }
+  BGV_NO_UNROLL for (int j = NWIN - 1; j >= 0; --j) {
+    BGV_NO_UNROLL for (int t = 0; t < 4; ++t) acc = jac_dbl(acc);
+    acc = jac_glv_step<false>(acc, tab, bgv_recode16_digit(a, ca, j));
+    acc = jac_glv_step<true>(acc, tab, bgv_recode16_digit(b, cb, j));
+  }
+  return jac_t<F>{acc.x, acc.y, acc.z};  // not NRVO (see jac_mul_x_abs)
+}
+
 BGV_HD bool g2_aff_on_curve(const g2_aff& a) {
   const fp2_t b = BGV_B2;
   return fp2_eq(fp2_sqr(a.y), fp2_add(fp2_mul(fp2_sqr(a.x), a.x), b));
@@ -427,6 +500,12 @@ BGV_HD bool g2_aff_on_curve(const g2_aff& a) {
 BGV_HD bool g2_in_subgroup(const g2_jac& p) {
   g2_jac q = jac_neg(jac_mul_x_abs(p));
   return jac_eq(g2_psi(p), q);
+}
+
+// the same test on an affine point, [|x|]P with mixed additions
+BGV_HD bool g2_in_subgroup_aff(const g2_aff& a) {
+  g2_jac q = jac_neg(jac_mul_x_abs_aff(a));
+  return jac_eq(g2_psi(jac_from_aff(a)), q);
 }
 
 // [x]P with x = -|x|

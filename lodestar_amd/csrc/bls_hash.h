@@ -246,6 +246,45 @@ BGV_NOINLINE g2_jac iso_map_g2_jac(const g2_jac& p) {
   return r;
 }
 
+// Doubling on E2' (dbl-2007-bl with a = A' = 240i; jac_dbl is the a = 0 form of E2).  Only the
+// sum of two equal SSWU points takes it, so it is written with the eager products.
+BGV_NOINLINE g2_jac e2p_dbl(const g2_jac& p) {
+  const fp2_t A = BGV_SSWU_A;
+  const fp2_t XX = fp2_sqr(p.x), YY = fp2_sqr(p.y), ZZ = fp2_sqr(p.z);
+  const fp2_t YYYY = fp2_sqr(YY);
+  const fp2_t S = fp2_dbl(fp2_sub(fp2_sub(fp2_sqr(fp2_add(p.x, YY)), XX), YYYY));
+  const fp2_t M = fp2_add(fp2_add(fp2_dbl(XX), XX), fp2_mul(A, fp2_sqr(ZZ)));
+  const fp2_t T = fp2_sub(fp2_sqr(M), fp2_dbl(S));
+  const fp2_t Y8 = fp2_dbl(fp2_dbl(fp2_dbl(YYYY)));
+  g2_jac r;
+  r.x = T;
+  r.y = fp2_sub(fp2_mul(M, fp2_sub(S, T)), Y8);
+  r.z = fp2_sub(fp2_sub(fp2_sqr(fp2_add(p.y, p.z)), YY), ZZ);
+  return r;
+}
+
+// Complete addition of two points of E2' (the SSWU outputs, never at infinity themselves): the
+// addition formulas do not involve the curve's coefficients, the doubling does.  Opposite points
+// give Z = 0, which iso_map_g2_jac maps to Z = 0.
+BGV_HD g2_jac e2p_add(const g2_jac& p, const g2_jac& q) {
+  bool hz, rz;
+  g2_jac r = jac_add_raw(p, q, &hz, &rz);
+  if (hz && rz) r = e2p_dbl(p);  // rare: equal SSWU points
+  return r;
+}
+
+// hash_to_G2 with one isogeny: the 3-isogeny is a group homomorphism E2' -> E2, so
+// iso(q0) + iso(q1) = iso(q0 + q1) with the sum taken on E2' (RFC 9380 6.6.3 notes the same for
+// the affine map).  The same point of G2 as hash_to_g2, by another Jacobian representative.
+BGV_NOINLINE g2_jac hash_to_g2_sum(const uint8_t* msg, uint32_t len) {
+  fp2_t u0, u1;
+  hash_to_field_fp2(&u0, &u1, msg, len);
+  const fp_t sm5 = fp_sqrt_minus5();
+  const g2_jac q0 = sswu_g2_jac(u0, sm5);
+  const g2_jac q1 = sswu_g2_jac(u1, sm5);
+  return g2_clear_cofactor(iso_map_g2_jac(e2p_add(q0, q1)));
+}
+
 // Full hash_to_G2 of one message: a Jacobian point in G2 (both maps in Jacobian form, no
 // inversion anywhere).
 BGV_NOINLINE g2_jac hash_to_g2(const uint8_t* msg, uint32_t len) {

@@ -1,9 +1,10 @@
 """Count Fp products per verify-kernel per set (roofline numerator).
 
-Builds tests/native/hostsim.cpp and tests/native/curvesim.cpp with -DBGV_COUNT_OPS (the
-kernels' own per-lane math compiled for the host with a counter in fp_mul / fp_sqr), runs each
-kernel body once on representative inputs and writes profiles/opcounts.json.  The bodies of
-k_prep's three tasks (what bgv_k_tasks.h task_sig / task_hash / task_pk call) are curvesim.cpp's.
+Builds tests/native/hostsim.cpp, tests/native/curvesim.cpp and tests/native/prepsim.cpp with
+-DBGV_COUNT_OPS (the kernels' own per-lane math compiled for the host with a counter in fp_mul /
+fp_sqr), runs each kernel body once on representative inputs and writes profiles/opcounts.json.
+The bodies of k_prep's three tasks (what bgv_k_tasks.h task_sig / task_hash / task_pk call) are
+prepsim.cpp's (sig, hash) and curvesim.cpp's (pk).
 Random-scalar steps are averaged over seeded 64-bit scalars.
 
     python tools/count_ops.py
@@ -23,6 +24,7 @@ from tests import hostsim as hs  # noqa: E402
 
 LIB = os.path.join(ROOT, "tests", "native", "libhostsim_count.so")
 LIB_PREP = os.path.join(ROOT, "tests", "native", "libcurvesim_count.so")
+LIB_TASKS = os.path.join(ROOT, "tests", "native", "libprepsim_count.so")
 
 
 def main():
@@ -30,18 +32,25 @@ def main():
                            os.path.join(ROOT, "tests", "native", "hostsim.cpp")])
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-DBGV_COUNT_OPS", "-o", LIB_PREP,
                            os.path.join(ROOT, "tests", "native", "curvesim.cpp")])
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-DBGV_COUNT_OPS", "-o", LIB_TASKS,
+                           os.path.join(ROOT, "tests", "native", "prepsim.cpp")])
     L = ctypes.CDLL(LIB)
     L.hs_count_mul.restype = ctypes.c_ulonglong
     L.hs_count_sqr.restype = ctypes.c_ulonglong
     C = ctypes.CDLL(LIB_PREP)
     C.cs_count_mul.restype = ctypes.c_ulonglong
     C.cs_count_sqr.restype = ctypes.c_ulonglong
+    T = ctypes.CDLL(LIB_TASKS)
+    T.ps_count_mul.restype = ctypes.c_ulonglong
+    T.ps_count_sqr.restype = ctypes.c_ulonglong
 
     def count(fn):
         L.hs_count_reset()
         C.cs_count_reset()
+        T.ps_count_reset()
         fn()
-        return int(L.hs_count_mul()) + int(C.cs_count_mul()), int(L.hs_count_sqr()) + int(C.cs_count_sqr())
+        return (int(L.hs_count_mul()) + int(C.cs_count_mul()) + int(T.ps_count_mul()),
+                int(L.hs_count_sqr()) + int(C.cs_count_sqr()) + int(T.ps_count_sqr()))
 
     rng = random.Random(7)
     sk = o.interop_secret_key(3)
@@ -52,11 +61,11 @@ def main():
     trials = 8
     acc = [0, 0]
     for _ in range(trials):
-        m, s = count(lambda: C.cs_k_sig_body(o.g2_compress(sig), ctypes.c_uint64(rng.getrandbits(64) | 1)))
+        m, s = count(lambda: T.ps_k_sig_body(o.g2_compress(sig), ctypes.c_uint64(rng.getrandbits(64) | 1)))
         acc[0] += m
         acc[1] += s
     out["k_sig"] = [acc[0] / trials, acc[1] / trials]
-    out["k_hash"] = list(count(lambda: C.cs_k_hash_body(msg)))
+    out["k_hash"] = list(count(lambda: T.ps_k_hash_body(msg)))
     for npk in (1, 128):
         acc = [0, 0]
         for _ in range(trials):
