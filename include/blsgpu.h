@@ -217,7 +217,20 @@ int bgv_committee_drop_range(bgv_ctx* ctx, uint32_t first_id, uint32_t count);
  * >= BGV_MAX_COMMITTEES, or fewer than `size` acceptances within BGV_SAMPLE_MAX_TRIES candidates
  * (where the reference's loop would go on; a zero balance is accepted on a random byte of 0
  * only); -BGV_E_BAD_INDEX: an active index at or past
- * bgv_pubkeys_count, or a marked one.  All or nothing: on any error the id does not exist. */
+ * bgv_pubkeys_count, or a marked one.  All or nothing: on any error the id does not exist.
+ *
+ * bgv_proposers_electra, bgv_sync_committee_put_electra: the same two calls under the acceptance
+ * rule of Electra (EIP-7251: the consensus spec's compute_proposer_index and
+ * get_next_sync_committee_indices draw 16 bits per candidate from that fork on).  v_i as above;
+ *   rand_i = LE16(sha256(seed | LE64(i div 16))[2 (i mod 16) .. 2 (i mod 16) + 2))
+ *   candidate i is accepted iff eff_incr16[v_i] * 65535 >= max_incr * rand_i
+ * eff_incr16 is EffectiveBalanceIncrements from Electra on (a Uint16Array: one uint16_t per
+ * validator index, n_eff of them) and max_incr MAX_EFFECTIVE_BALANCE_ELECTRA /
+ * EFFECTIVE_BALANCE_INCREMENT (2048 on mainnet), 1..65535.  Everything said of bgv_proposers and
+ * bgv_sync_committee_put above holds for them -- the argument checks, BGV_NO_PROPOSER, the
+ * BGV_SAMPLE_MAX_TRIES cap, all or nothing, -BGV_E_BAD_INDEX, the committee being a committee in
+ * every respect on every device -- with "max_incr 0 or > 65535" in place of "0 or > 255" and a
+ * zero balance accepted on a random value of 0 only. */
 #define BGV_NO_PROPOSER 0xFFFFFFFFu
 #define BGV_SAMPLE_MAX_TRIES 65536u
 int bgv_proposers(bgv_ctx* ctx, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active_indices,
@@ -226,6 +239,12 @@ int bgv_proposers(bgv_ctx* ctx, const uint8_t* seeds32, uint32_t n_seeds, const 
 int bgv_sync_committee_put(bgv_ctx* ctx, uint32_t id, const uint8_t seed[32], const uint32_t* active_indices,
                            size_t n_active, const uint8_t* eff_incr, size_t n_eff, uint32_t max_incr, uint32_t size,
                            uint32_t rounds, uint32_t* out_indices, uint8_t out_agg48[48]);
+int bgv_proposers_electra(bgv_ctx* ctx, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active_indices,
+                          size_t n_active, const uint16_t* eff_incr16, size_t n_eff, uint32_t max_incr,
+                          uint32_t rounds, uint32_t* out_proposers);
+int bgv_sync_committee_put_electra(bgv_ctx* ctx, uint32_t id, const uint8_t seed[32], const uint32_t* active_indices,
+                                   size_t n_active, const uint16_t* eff_incr16, size_t n_eff, uint32_t max_incr,
+                                   uint32_t size, uint32_t rounds, uint32_t* out_indices, uint8_t out_agg48[48]);
 
 /* The pubkeys of one set as committee members: member k takes part iff
  * (bits[k >> 3] >> (k & 7)) & 1 (SSZ bit order); bits holds ceil(n_bits / 8) bytes.

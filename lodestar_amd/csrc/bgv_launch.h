@@ -137,10 +137,11 @@ hipError_t bgv_launch_shuffle(const uint8_t seed[32], uint32_t n, uint32_t round
                               hipStream_t st);
 hipError_t bgv_launch_shuffle_dir(bgv_dcommittee* dir, const uint32_t* handles, uint32_t nh, uint32_t base, uint32_t n,
                                   uint32_t count, hipStream_t st);
-// Balance-weighted sampling (bgv_k_sample.hip, bgv_sample.h).  One pass: k_sample_eval over
-// `window` candidates (a multiple of 256) of each of the n_todo seeds in todo, from the seed's
-// state.next on, then k_sample_pick appending the accepted ones among the first `count` to
-// picks[seed * want ..) and advancing the seed's state.  vals / flags: n_todo * window entries.
+// Balance-weighted sampling (bgv_k_sample.hip, bgv_sample.h).  One pass: k_sample_eval (under the
+// 16-bit rule k_sample_eval16) over `window` candidates (a multiple of 256) of each of the n_todo
+// seeds in todo, from the seed's state.next on, then k_sample_pick appending the accepted ones
+// among the first `count` to picks[seed * want ..) and advancing the seed's state.  vals / flags:
+// n_todo * window entries.
 struct shuf_seed;
 struct samp_state;
 struct bgv_sample_in {
@@ -148,9 +149,10 @@ struct bgv_sample_in {
   samp_state* state;       // per seed
   const uint32_t* active;  // n indices, each below the length of eff
   uint32_t n;
-  const uint8_t* eff;
+  const void* eff;  // uint8_t per validator index (SAMP_RULE_BYTE), uint16_t (SAMP_RULE_U16)
   uint32_t max_incr, rounds, limit, want;
   uint32_t* picks;  // want per seed
+  uint32_t rule;    // samp_rule_id: selects k_sample_eval or k_sample_eval16
 };
 hipError_t bgv_launch_sample_pass(const bgv_sample_in& in, const uint32_t* todo, uint32_t n_todo, uint32_t window,
                                   uint32_t count, uint32_t* vals, uint8_t* flags, hipStream_t st);

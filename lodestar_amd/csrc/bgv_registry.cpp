@@ -299,7 +299,7 @@ int bgv_committee_drop_range(bgv_ctx* c, uint32_t first_id, uint32_t count) {
 static_assert(BGV_SAMPLE_CAP == BGV_SAMPLE_MAX_TRIES, "bgv_sample.h plans its passes within the public cap");
 
 namespace {
-// samp_run's device: one pass is k_sample_eval + k_sample_pick over the seeds still short, on the
+// samp_run's device: one pass is k_sample_eval (the rule's: in.rule) + k_sample_pick over the seeds still short, on the
 // utility stream, and one synchronize that reads the seeds' states back.
 struct SampleDev {
   Device& d;
@@ -324,10 +324,18 @@ struct SampleDev {
   }
 };
 
-bool sample_args_ok(const uint32_t* active, size_t n_active, const uint8_t* eff, size_t n_eff, uint32_t max_incr,
-                    uint32_t rounds) {
+// What the rule sets: the balance table's element size and the largest max_incr.
+size_t sample_eff_bytes(samp_rule_id rule) {
+  return rule == SAMP_RULE_U16 ? sizeof(samp_rule16::eff_t) : sizeof(samp_rule8::eff_t);
+}
+uint32_t sample_max_incr(samp_rule_id rule) {
+  return rule == SAMP_RULE_U16 ? samp_rule16::MAX_INCR : samp_rule8::MAX_INCR;
+}
+
+bool sample_args_ok(const uint32_t* active, size_t n_active, const void* eff, size_t n_eff, uint32_t max_incr,
+                    uint32_t rounds, samp_rule_id rule) {
   if (!active || !eff || n_active < 1 || n_active > BGV_SHUFFLE_MAX_N || n_eff < 1 || n_eff > (size_t)UINT32_MAX ||
-      rounds > BGV_SHUFFLE_MAX_ROUNDS || max_incr < 1 || max_incr > 255)
+      rounds > BGV_SHUFFLE_MAX_ROUNDS || max_incr < 1 || max_incr > sample_max_incr(rule))
     return false;
   for (size_t i = 0; i < n_active; ++i)
     if (active[i] >= n_eff) return false;
@@ -335,10 +343,12 @@ bool sample_args_ok(const uint32_t* active, size_t n_active, const uint8_t* eff,
 }
 
 // The first `want` accepted candidates of each seed, sampled on the first device: st[s].have of
-// them at picks[s * want ..).  Under the shared cache_mu (the devices stay); takes util_mu.
+// them at picks[s * want ..).  eff holds n_eff elements of the rule's type.  Under the shared
+// cache_mu (the devices stay); takes util_mu.
 int sample_run(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, uint32_t n,
-               const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t rounds, uint32_t want, uint32_t limit,
-               std::vector<samp_state>& st, std::vector<uint32_t>& picks) {
+               const void* eff, size_t n_eff, samp_rule_id rule, uint32_t max_incr, uint32_t rounds, uint32_t want,
+               uint32_t limit, std::vector<samp_state>& st, std::vector<uint32_t>& picks) {
+  const size_t eff_bytes = n_eff * sample_eff_bytes(rule);
   std::vector<shuf_seed> seeds(n_seeds);
   for (uint32_t s = 0; s < n_seeds; ++s) seeds[s] = shuf_seed_load(seeds32 + 32 * (size_t)s);
   picks.assign((size_t)n_seeds * want, 0);
@@ -350,15 +360,15 @@ int sample_run(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint3
   samp_state* dstate = nullptr;
   uint32_t *dact = nullptr, *dpicks = nullptr, *dtodo = nullptr;
   uint8_t* deff = nullptr;
-  if (sc.alloc(&dseeds, n_seeds) || sc.alloc(&dstate, n_seeds) || sc.alloc(&dact, n) || sc.alloc(&deff, n_eff) ||
+  if (sc.alloc(&dseeds, n_seeds) || sc.alloc(&dstate, n_seeds) || sc.alloc(&dact, n) || sc.alloc(&deff, eff_bytes) ||
       sc.alloc(&dpicks, picks.size()) || sc.alloc(&dtodo, n_seeds))
     return -BGV_E_DEVICE;
   HIPCHK(hipMemcpyAsync(dseeds, seeds.data(), sizeof(shuf_seed) * n_seeds, hipMemcpyHostToDevice, d.stream));
   HIPCHK(hipMemsetAsync(dstate, 0, sizeof(samp_state) * n_seeds, d.stream));
   HIPCHK(hipMemcpyAsync(dact, active, 4 * (size_t)n, hipMemcpyHostToDevice, d.stream));
-  HIPCHK(hipMemcpyAsync(deff, eff, n_eff, hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(deff, eff, eff_bytes, hipMemcpyHostToDevice, d.stream));
   HIPCHK(hipMemsetAsync(dpicks, 0, 4 * picks.size(), d.stream));
-  const bgv_sample_in in{dseeds, dstate, dact, n, deff, max_incr, rounds, limit, want, dpicks};
+  const bgv_sample_in in{dseeds, dstate, dact, n, deff, max_incr, rounds, limit, want, dpicks, rule};
   SampleDev dev{d, sc, in, n_seeds, dtodo};
   if (int rc = samp_run(dev, n_seeds, want, limit, st)) return rc;
   sc.enqueued();
@@ -382,14 +392,13 @@ void g1_compress(uint8_t out48[48], const uint8_t in96[96]) {
   memcpy(out48, in96, 48);
   out48[0] |= cmp > 0 ? 0xA0 : 0x80;
 }
-}  // namespace
 
-extern "C" {
-
-int bgv_proposers(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, size_t n_active,
-                  const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t rounds, uint32_t* out_proposers) {
+// bgv_proposers / bgv_proposers_electra: the same call under either rule
+int proposers_by_rule(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, size_t n_active,
+                      const void* eff, size_t n_eff, samp_rule_id rule, uint32_t max_incr, uint32_t rounds,
+                      uint32_t* out_proposers) {
   if (!c || !seeds32 || !out_proposers || n_seeds < 1 || n_seeds > BGV_SAMPLE_MAX_SEEDS ||
-      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds))
+      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds, rule))
     return -BGV_E_ARG;
   const uint32_t limit = samp_limit(n_active, true);
   std::vector<samp_state> st;
@@ -397,8 +406,8 @@ int bgv_proposers(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const ui
   {
     std::shared_lock<std::shared_mutex> clk(c->cache_mu);  // bgv_close frees the devices under the exclusive lock
     if (c->closed) return -BGV_E_CLOSED;
-    if (int rc = sample_run(c, seeds32, n_seeds, active, (uint32_t)n_active, eff, n_eff, max_incr, rounds, 1, limit, st,
-                            picks))
+    if (int rc = sample_run(c, seeds32, n_seeds, active, (uint32_t)n_active, eff, n_eff, rule, max_incr, rounds, 1,
+                            limit, st, picks))
       return rc;
   }
   // every candidate rejected: the reference's -1 when that was the whole list, else the cap was hit
@@ -408,16 +417,17 @@ int bgv_proposers(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const ui
   return BGV_OK;
 }
 
+// bgv_sync_committee_put / bgv_sync_committee_put_electra.
 // The next sync committee: sampled on the first device, then stored on every device exactly as
 // bgv_committee_put stores a list (committee_put_locked: checks, pool range, directory entry,
 // k_committee_total).  put_mu is held throughout, so neither the cache nor the id changes between
 // the sampling and the store; the aggregate is read through bgv_aggregate_committee_bits once
 // the committee exists, and the id is dropped again should that fail.
-int bgv_sync_committee_put(bgv_ctx* c, uint32_t id, const uint8_t seed[32], const uint32_t* active, size_t n_active,
-                           const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t size, uint32_t rounds,
-                           uint32_t* out_indices, uint8_t out_agg48[48]) {
+int sync_committee_put_by_rule(bgv_ctx* c, uint32_t id, const uint8_t seed[32], const uint32_t* active,
+                               size_t n_active, const void* eff, size_t n_eff, samp_rule_id rule, uint32_t max_incr,
+                               uint32_t size, uint32_t rounds, uint32_t* out_indices, uint8_t out_agg48[48]) {
   if (!c || !seed || id >= BGV_MAX_COMMITTEES || size < 1 || size > BGV_SAMPLE_MAX_WANT ||
-      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds))
+      !sample_args_ok(active, n_active, eff, n_eff, max_incr, rounds, rule))
     return -BGV_E_ARG;
   std::lock_guard<std::mutex> plk(c->put_mu);
   std::vector<samp_state> st;
@@ -433,7 +443,7 @@ int bgv_sync_committee_put(bgv_ctx* c, uint32_t id, const uint8_t seed[32], cons
     const bool marks = !c->bad_pk.empty();
     for (size_t i = 0; i < n_active; ++i)
       if (active[i] >= npk || (marks && c->bad_pk.count(active[i]))) return -BGV_E_BAD_INDEX;
-    if (int rc = sample_run(c, seed, 1, active, (uint32_t)n_active, eff, n_eff, max_incr, rounds, size,
+    if (int rc = sample_run(c, seed, 1, active, (uint32_t)n_active, eff, n_eff, rule, max_incr, rounds, size,
                             samp_limit(n_active, false), st, picks))
       return rc;
     if (st[0].have < size) return -BGV_E_ARG;  // the cap
@@ -454,6 +464,33 @@ int bgv_sync_committee_put(bgv_ctx* c, uint32_t id, const uint8_t seed[32], cons
   }
   if (out_indices) memcpy(out_indices, picks.data(), 4 * (size_t)size);
   return BGV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bgv_proposers(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active, size_t n_active,
+                  const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t rounds, uint32_t* out_proposers) {
+  return proposers_by_rule(c, seeds32, n_seeds, active, n_active, eff, n_eff, SAMP_RULE_BYTE, max_incr, rounds,
+                           out_proposers);
+}
+int bgv_proposers_electra(bgv_ctx* c, const uint8_t* seeds32, uint32_t n_seeds, const uint32_t* active,
+                          size_t n_active, const uint16_t* eff16, size_t n_eff, uint32_t max_incr, uint32_t rounds,
+                          uint32_t* out_proposers) {
+  return proposers_by_rule(c, seeds32, n_seeds, active, n_active, eff16, n_eff, SAMP_RULE_U16, max_incr, rounds,
+                           out_proposers);
+}
+int bgv_sync_committee_put(bgv_ctx* c, uint32_t id, const uint8_t seed[32], const uint32_t* active, size_t n_active,
+                           const uint8_t* eff, size_t n_eff, uint32_t max_incr, uint32_t size, uint32_t rounds,
+                           uint32_t* out_indices, uint8_t out_agg48[48]) {
+  return sync_committee_put_by_rule(c, id, seed, active, n_active, eff, n_eff, SAMP_RULE_BYTE, max_incr, size, rounds,
+                                    out_indices, out_agg48);
+}
+int bgv_sync_committee_put_electra(bgv_ctx* c, uint32_t id, const uint8_t seed[32], const uint32_t* active,
+                                   size_t n_active, const uint16_t* eff16, size_t n_eff, uint32_t max_incr,
+                                   uint32_t size, uint32_t rounds, uint32_t* out_indices, uint8_t out_agg48[48]) {
+  return sync_committee_put_by_rule(c, id, seed, active, n_active, eff16, n_eff, SAMP_RULE_U16, max_incr, size,
+                                    rounds, out_indices, out_agg48);
 }
 
 namespace {

@@ -2,7 +2,8 @@
 // getNextSyncCommitteeIndices (state-transition/src/util/seed.ts).  Plain host/device functions
 // (no HIP types) over bgv_shuffle.h's swap-or-not arithmetic: k_sample_eval / k_sample_pick
 // (bgv_k_sample.hip) run them per thread, the host (bgv_registry.cpp) runs the pass loop at the
-// end of this file, and tests/native/samplesim.cpp runs all of it on a CPU.
+// end of this file, and tests/native/samplesim.cpp (byte rule) and samplesim_electra.cpp (16-bit
+// rule) run all of it on a CPU.
 //
 // Candidate i = 0, 1, 2, ... of a seed over n active indices:
 //   v_i    = active[compute_shuffled_index(i mod n, n, seed)]
@@ -12,6 +13,12 @@
 // examined a WINDOW at a time: every candidate of the window is evaluated (one thread each), then
 // an ordered compaction appends the accepted ones to the picks.  A seed that is still short gets a
 // further window; no candidate at or past `limit` is ever accepted, which bounds the work.
+//
+// That is the BYTE rule (phase0 .. Deneb).  The U16 rule (Electra, EIP-7251) draws 16 bits:
+//   rand_i = LE16(sha256(seed | LE64(i div 16))[2 (i mod 16) ..])   (16 candidates per digest)
+//   accepted iff eff[v_i] * 65535 >= max_incr * rand_i              (eff: uint16_t per validator)
+// Only the draw, the table's element and the acceptance test differ (samp_rule8 / samp_rule16
+// below); the walk, the pivots, the compaction, the pass loop, the cap and the limit are shared.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,6 +34,9 @@
 #define BGV_SAMPLE_MAX_WANT 65536u
 #define BGV_SAMPLE_PASS_ITEMS (1u << 22)  // candidates of one pass over all its seeds, at most (20 MB of results)
 
+// which acceptance rule a call samples by (bgv_sample_in::rule)
+enum samp_rule_id : uint32_t { SAMP_RULE_BYTE = 0, SAMP_RULE_U16 = 1 };
+
 // a seed's progress, kept on the device between passes
 struct samp_state {
   uint32_t have;  // picks so far (<= want)
@@ -36,7 +46,8 @@ struct samp_state {
 // ---------------------------------------------------------------------------
 // per candidate
 // ---------------------------------------------------------------------------
-// sha256(seed | LE64(q)): the random bytes of candidates 32 q .. 32 q + 31
+// sha256(seed | LE64(q)): the random bytes of candidates 32 q .. 32 q + 31 (byte rule), or of
+// candidates 16 q .. 16 q + 15, two bytes each (16-bit rule)
 BGV_HD void samp_hash_rand(uint32_t out[8], const shuf_seed& s, uint64_t q) {
   uint32_t blk[16];
   BGV_UNROLL for (int j = 0; j < 8; ++j) blk[j] = s.w[j];
@@ -74,29 +85,93 @@ BGV_HD uint32_t samp_walk(uint32_t i, uint32_t n, uint32_t rounds, const shuf_se
 
 BGV_HD bool samp_accept(uint32_t eff, uint32_t max_incr, uint32_t byte) { return eff * 255u >= max_incr * byte; }
 
-// What one block of k_sample_eval shares: the seed's pivots and the digests of the random bytes of
-// its BGV_SAMPLE_BLOCK candidates base .. base + 255 (base a multiple of 32).  Thread t's part.
-#define BGV_SAMPLE_RAND_DIGESTS (BGV_SAMPLE_BLOCK / 32u)
-BGV_HD void samp_setup_item(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base, uint32_t* piv,
-                            uint32_t* rnd /* BGV_SAMPLE_RAND_DIGESTS x 8 words */) {
+// 16-bit value k (< 16) of a digest held as SHA-256's 8 big-endian words: d[2k] | d[2k+1] << 8 of
+// its bytes, which is one half-word of word k / 2 with its two bytes swapped.  The word is picked
+// without indexing registers, as samp_walk picks its bit's word.
+BGV_HD uint32_t samp_digest_u16(const uint32_t* d, uint32_t k) {
+  const uint32_t j = k >> 1;
+  uint32_t w = d[0];
+  BGV_UNROLL for (uint32_t m = 1; m < 8; ++m) w = j == m ? d[m] : w;
+  const uint32_t h = (w >> (16u - 16u * (k & 1u))) & 0xffffu;  // bytes 2k (high) and 2k+1 (low)
+  return (h >> 8) | ((h & 0xffu) << 8);
+}
+// eff, max_incr and rand are all at most 65535, so both products fit 32 bits:
+// 65535 * 65535 = 4294836225 < 2^32 = 4294967296.
+BGV_HD bool samp_accept16(uint32_t eff, uint32_t max_incr, uint32_t rand) { return eff * 65535u >= max_incr * rand; }
+
+// The two rules: what depends on the draw, and nothing else.
+struct samp_rule8 {
+  typedef uint8_t eff_t;
+  static constexpr uint32_t SHIFT = 5;  // log2 of the candidates one digest serves
+  static constexpr uint32_t MAX_INCR = 255;
+  static BGV_HD uint32_t draw(const uint32_t* d, uint32_t k) { return samp_digest_byte(d, k); }
+  static BGV_HD bool accept(uint32_t eff, uint32_t max_incr, uint32_t r) { return samp_accept(eff, max_incr, r); }
+};
+struct samp_rule16 {
+  typedef uint16_t eff_t;
+  static constexpr uint32_t SHIFT = 4;
+  static constexpr uint32_t MAX_INCR = 65535;
+  static BGV_HD uint32_t draw(const uint32_t* d, uint32_t k) { return samp_digest_u16(d, k); }
+  static BGV_HD bool accept(uint32_t eff, uint32_t max_incr, uint32_t r) { return samp_accept16(eff, max_incr, r); }
+};
+// digests behind the draws of one block's BGV_SAMPLE_BLOCK candidates: 8 (byte rule), 16 (16-bit rule)
+template <class R>
+constexpr uint32_t samp_rand_digests() {
+  return BGV_SAMPLE_BLOCK >> R::SHIFT;
+}
+
+// What one block of k_sample_eval shares: the seed's pivots and the digests of the draws of its
+// BGV_SAMPLE_BLOCK candidates base .. base + 255 (base a multiple of 256, hence of 32 and of 16).
+// Thread t's part.
+template <class R>
+BGV_HD void samp_setup_item_r(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base, uint32_t* piv,
+                              uint32_t* rnd /* samp_rand_digests<R>() x 8 words */) {
+  constexpr uint32_t ND = samp_rand_digests<R>();
   if (t < rounds && n >= 2) piv[t] = shuf_pivot(s, t, n);
   // the last threads of the block: with the usual 90 rounds they hash no pivot
-  if (t >= BGV_SAMPLE_BLOCK - BGV_SAMPLE_RAND_DIGESTS && t < BGV_SAMPLE_BLOCK) {
-    const uint32_t j = t - (BGV_SAMPLE_BLOCK - BGV_SAMPLE_RAND_DIGESTS);
+  if (t >= BGV_SAMPLE_BLOCK - ND && t < BGV_SAMPLE_BLOCK) {
+    const uint32_t j = t - (BGV_SAMPLE_BLOCK - ND);
     uint32_t d[8];
-    samp_hash_rand(d, s, (uint64_t)(base >> 5) + j);
+    samp_hash_rand(d, s, (uint64_t)(base >> R::SHIFT) + j);
     BGV_UNROLL for (int w = 0; w < 8; ++w) rnd[8u * j + w] = d[w];
   }
 }
 // Candidate base + t: its validator index into *v, and whether it is accepted (never at or past limit).
+template <class R>
+BGV_HD bool samp_eval_item_r(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base, uint32_t limit,
+                             const uint32_t* piv, const uint32_t* rnd, const uint32_t* active,
+                             const typename R::eff_t* eff, uint32_t max_incr, uint32_t* v) {
+  const uint32_t i = base + t;
+  *v = active[samp_walk(i % n, n, rounds, s, piv)];
+  const uint32_t r = R::draw(rnd + 8u * ((i >> R::SHIFT) - (base >> R::SHIFT)), i & ((1u << R::SHIFT) - 1u));
+  return i < limit && R::accept(eff[*v], max_incr, r);
+}
+
+// the byte rule under its own names
+#define BGV_SAMPLE_RAND_DIGESTS (BGV_SAMPLE_BLOCK / 32u)
+BGV_HD void samp_setup_item(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base, uint32_t* piv,
+                            uint32_t* rnd /* BGV_SAMPLE_RAND_DIGESTS x 8 words */) {
+  samp_setup_item_r<samp_rule8>(t, s, n, rounds, base, piv, rnd);
+}
 BGV_HD bool samp_eval_item(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base, uint32_t limit,
                            const uint32_t* piv, const uint32_t* rnd, const uint32_t* active, const uint8_t* eff,
                            uint32_t max_incr, uint32_t* v) {
-  const uint32_t i = base + t;
-  *v = active[samp_walk(i % n, n, rounds, s, piv)];
-  const uint32_t byte = samp_digest_byte(rnd + 8u * ((i >> 5) - (base >> 5)), i & 31u);
-  return i < limit && samp_accept(eff[*v], max_incr, byte);
+  return samp_eval_item_r<samp_rule8>(t, s, n, rounds, base, limit, piv, rnd, active, eff, max_incr, v);
 }
+// ... and the 16-bit rule
+#define BGV_SAMPLE_RAND_DIGESTS16 (BGV_SAMPLE_BLOCK / 16u)
+BGV_HD void samp_setup_item16(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base,
+                              uint32_t* piv, uint32_t* rnd /* BGV_SAMPLE_RAND_DIGESTS16 x 8 words */) {
+  samp_setup_item_r<samp_rule16>(t, s, n, rounds, base, piv, rnd);
+}
+BGV_HD bool samp_eval_item16(uint32_t t, const shuf_seed& s, uint32_t n, uint32_t rounds, uint32_t base,
+                             uint32_t limit, const uint32_t* piv, const uint32_t* rnd, const uint32_t* active,
+                             const uint16_t* eff, uint32_t max_incr, uint32_t* v) {
+  return samp_eval_item_r<samp_rule16>(t, s, n, rounds, base, limit, piv, rnd, active, eff, max_incr, v);
+}
+static_assert(samp_rand_digests<samp_rule8>() == BGV_SAMPLE_RAND_DIGESTS &&
+                  samp_rand_digests<samp_rule16>() == BGV_SAMPLE_RAND_DIGESTS16,
+              "a block's digests follow from the candidates one digest serves");
 
 // ---------------------------------------------------------------------------
 // ordered compaction (k_sample_pick)

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = [
     "bgv_verify_partial", "bgv_final_verify", "bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split",
     "bgv_committee_put", "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
     "bgv_aggregate_committee_bits", "bgv_shuffling_put", "bgv_committee_drop_range",
-    "bgv_proposers", "bgv_sync_committee_put",
+    "bgv_proposers", "bgv_sync_committee_put", "bgv_proposers_electra", "bgv_sync_committee_put_electra",
     "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
 ]
 
@@ -140,6 +140,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_committee_drop_range": ([P, U32, U32], ctypes.c_int),
             "bgv_proposers": ([P, P, U32, P, SZ, P, SZ, U32, U32, P], ctypes.c_int),
             "bgv_sync_committee_put": ([P, U32, P, P, SZ, P, SZ, U32, U32, U32, P, P], ctypes.c_int),
+            "bgv_proposers_electra": ([P, P, U32, P, SZ, P, SZ, U32, U32, P], ctypes.c_int),
+            "bgv_sync_committee_put_electra": ([P, U32, P, P, SZ, P, SZ, U32, U32, U32, P, P], ctypes.c_int),
             "bgv_verify_spans": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P], ctypes.c_int),
             "bgv_verify_spans_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, DONE_FN, P], ctypes.c_int),
             "bgv_aggregate_span": ([P, P, P], ctypes.c_int),
@@ -149,6 +151,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                         "bgv_committee_drop", "bgv_verify_bits", "bgv_verify_bits_async",
                         "bgv_aggregate_committee_bits", "bgv_shuffling_put",
                         "bgv_committee_drop_range", "bgv_proposers", "bgv_sync_committee_put",
+                        "bgv_proposers_electra", "bgv_sync_committee_put_electra",
                         "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
@@ -308,6 +311,47 @@ class Context:
         agg = ctypes.create_string_buffer(48)
         _check(self.lib.bgv_sync_committee_put(self._h, committee_id, _buf(bytes(seed)), act.ctypes.data, act.size,
                                                eff.ctypes.data, eff.size, max_incr, size, rounds, out.ctypes.data, agg))
+        return out[:size], agg.raw
+
+    @staticmethod
+    def _eff16(eff_incr16):
+        """The Electra balance table as a contiguous uint16 array; values that do not fit are an
+        error, never wrapped."""
+        import numpy as np
+        a = np.asarray(eff_incr16)
+        if a.dtype != np.uint16:
+            if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 65535):
+                raise ValueError("eff_incr16: integers 0..65535 expected")
+            a = a.astype(np.uint16)
+        return np.ascontiguousarray(a.reshape(-1))
+
+    def proposers_electra(self, seeds: Sequence[bytes], active_indices: Sequence[int], eff_incr16,
+                          max_incr: int = 2048, rounds: int = 90) -> list:
+        """proposers() under Electra's rule (bgv_proposers_electra, EIP-7251): 16 random bits per
+        candidate and eff_incr16, anything convertible to np.uint16, one element per validator
+        index (values above 65535 raise ValueError)."""
+        import numpy as np
+        assert all(len(s) == 32 for s in seeds)
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        eff = self._eff16(eff_incr16)
+        out = np.empty(max(1, len(seeds)), dtype=np.uint32)
+        _check(self.lib.bgv_proposers_electra(self._h, _buf(b"".join(seeds)), len(seeds), act.ctypes.data, act.size,
+                                              eff.ctypes.data, eff.size, max_incr, rounds, out.ctypes.data))
+        return [None if v == NO_PROPOSER else int(v) for v in out[:len(seeds)]]
+
+    def sync_committee_put_electra(self, committee_id: int, seed: bytes, active_indices: Sequence[int], eff_incr16,
+                                   max_incr: int = 2048, size: int = 512, rounds: int = 90):
+        """sync_committee_put() under Electra's rule (bgv_sync_committee_put_electra); eff_incr16 as
+        for proposers_electra.  Returns (indices as a numpy uint32 array, the 48-byte aggregate)."""
+        import numpy as np
+        assert len(seed) == 32
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        eff = self._eff16(eff_incr16)
+        out = np.empty(max(1, size), dtype=np.uint32)
+        agg = ctypes.create_string_buffer(48)
+        _check(self.lib.bgv_sync_committee_put_electra(self._h, committee_id, _buf(bytes(seed)), act.ctypes.data,
+                                                       act.size, eff.ctypes.data, eff.size, max_incr, size, rounds,
+                                                       out.ctypes.data, agg))
         return out[:size], agg.raw
 
     def committee_drop_range(self, first_id: int, count: int) -> int:

@@ -44,6 +44,23 @@ const PUBKEY_RUN = 8192;
 const NO_PROPOSER = 0xffffffff; // BGV_NO_PROPOSER
 // include/blsgpu.h: BGV_BLST_* decode statuses are 1..19 (library codes start at 20)
 const toUint8Array = (v) => (v instanceof Uint8Array ? v : Uint8Array.from(v));
+// effectiveBalanceIncrements for the sampling rule: bytes under "phase0"; under "electra" a
+// Uint16Array, with a Uint8Array or a number array widened element by element (never
+// reinterpreted) and numbers that do not fit 16 bits refused, not wrapped
+function samplingTable(v, rule) {
+  if (rule === undefined || rule === "phase0") return toUint8Array(v);
+  if (rule !== "electra") throw new TypeError(`blsgpu: unknown sampling rule ${rule}`);
+  if (v instanceof Uint16Array) return v;
+  if (!(v instanceof Uint8Array) && !Array.isArray(v))
+    throw new TypeError("blsgpu: effectiveBalanceIncrements must be a Uint16Array, a Uint8Array or a number array");
+  const out = new Uint16Array(v.length);
+  for (let i = 0; i < v.length; i++) {
+    if (!Number.isInteger(v[i]) || v[i] < 0 || v[i] > 0xffff)
+      throw new RangeError(`blsgpu: effectiveBalanceIncrements[${i}] = ${v[i]} does not fit 16 bits`);
+    out[i] = v[i];
+  }
+  return out;
+}
 const isBlstDecodeCode = (code) => typeof code === "number" && code <= -1 && code >= -19;
 
 // One contiguous run of queued validator keys: indices [first, first + n), their 48-byte
@@ -302,10 +319,12 @@ class BlsGpuVerifier {
    * device call: the per-slot seeds sha256(epochSeed | LE64(slot)) are hashed here, the balance-
    * weighted sampling (computeProposerIndex) runs on the device off the event loop.  Resolves to a
    * number[] with -1 where every candidate was rejected, as the reference.  The pubkey cache is
-   * not involved.
+   * not involved.  opts.rule: "phase0" (the default: one random byte per candidate, byte
+   * increments) or "electra" (EIP-7251: 16 random bits, effectiveBalanceIncrements a Uint16Array
+   * or a number array; a Uint8Array is widened).
    */
   async computeProposers(epochSeed, startSlot, activeIndices, effectiveBalanceIncrements, opts) {
-    const {slots, maxEffectiveBalanceIncrement, rounds} = opts;
+    const {slots, maxEffectiveBalanceIncrement, rounds, rule} = opts;
     const seeds = new Uint8Array(32 * slots);
     const msg = Buffer.alloc(40);
     Buffer.from(epochSeed.buffer, epochSeed.byteOffset, epochSeed.byteLength).copy(msg, 0, 0, 32);
@@ -314,8 +333,9 @@ class BlsGpuVerifier {
       seeds.set(crypto.createHash("sha256").update(msg).digest(), 32 * k);
     }
     const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
-    const eff = toUint8Array(effectiveBalanceIncrements);
-    const out = await addon.proposers(this.ctx, seeds, active, eff, maxEffectiveBalanceIncrement, rounds);
+    const eff = samplingTable(effectiveBalanceIncrements, rule);
+    const call = rule === "electra" ? addon.proposersElectra : addon.proposers;
+    const out = await call(this.ctx, seeds, active, eff, maxEffectiveBalanceIncrement, rounds);
     return Array.from(out, (v) => (v === NO_PROPOSER ? -1 : v));
   }
 
@@ -324,13 +344,15 @@ class BlsGpuVerifier {
    * INTEGRATION.md §2c): the first `size` candidates accepted by balance become committee `id`,
    * repeats kept, on every device, exactly as after committeePut of the same list.  Resolves to
    * {indices: Uint32Array, aggregatePubkey: Uint8Array(48)}.  The queued pubkeys go first.
+   * opts.rule as for computeProposers.
    */
   async syncCommitteePut(id, seed, activeIndices, effectiveBalanceIncrements, opts) {
-    const {size, maxEffectiveBalanceIncrement, rounds} = opts;
+    const {size, maxEffectiveBalanceIncrement, rounds, rule} = opts;
+    const eff = samplingTable(effectiveBalanceIncrements, rule);
     await this.flushPubkeys();
     const active = activeIndices instanceof Uint32Array ? activeIndices : Uint32Array.from(activeIndices);
-    const eff = toUint8Array(effectiveBalanceIncrements);
-    return addon.syncCommitteePut(this.ctx, id, seed, active, eff, maxEffectiveBalanceIncrement, size, rounds);
+    const call = rule === "electra" ? addon.syncCommitteePutElectra : addon.syncCommitteePut;
+    return call(this.ctx, id, seed, active, eff, maxEffectiveBalanceIncrement, size, rounds);
   }
 
   /** Drops the live ids of firstId .. firstId + count - 1 (an epoch's committees); returns how many. */

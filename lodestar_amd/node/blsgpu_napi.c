@@ -493,15 +493,19 @@ static napi_value js_shuffling_put(napi_env env, napi_callback_info info) {
  * and syncCommitteePut(ctx, id, seed: Uint8Array(32), activeIndices, effectiveBalanceIncrements,
  * maxIncr, size, rounds) -> Promise<{indices: Uint32Array(size), aggregatePubkey: Uint8Array(48)}>
  * (bgv_sync_committee_put), both on a libuv pool thread like shufflingPut and rejecting with an
- * Error whose .bgvCode is the negative library code. */
+ * Error whose .bgvCode is the negative library code.  proposersElectra and syncCommitteePutElectra
+ * are the same two under Electra's rule (bgv_proposers_electra, bgv_sync_committee_put_electra):
+ * effectiveBalanceIncrements is a Uint16Array, everything else as above. */
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
   napi_ref ctx_ref, seed_ref, act_ref, eff_ref, out_ref, agg_ref;
   bgv_ctx* c;
-  int sync; /* syncCommitteePut, else proposers */
+  int sync;    /* syncCommitteePut, else proposers */
+  int electra; /* eff holds uint16_t, the calls are the _electra ones */
   uint32_t id, n_seeds, max_incr, size, rounds;
-  const uint8_t *seeds, *eff;
+  const uint8_t* seeds;
+  const void* eff;
   const uint32_t* active;
   size_t n, n_eff;
   uint32_t* out;
@@ -512,12 +516,18 @@ typedef struct {
 static void samp_execute(napi_env env, void* data) {
   (void)env;
   samp_req* r = (samp_req*)data;
-  if (r->sync)
-    r->rc = bgv_sync_committee_put(r->c, r->id, r->seeds, r->active, r->n, r->eff, r->n_eff, r->max_incr, r->size,
-                                   r->rounds, r->out, r->agg);
+  if (r->sync && r->electra)
+    r->rc = bgv_sync_committee_put_electra(r->c, r->id, r->seeds, r->active, r->n, (const uint16_t*)r->eff, r->n_eff,
+                                           r->max_incr, r->size, r->rounds, r->out, r->agg);
+  else if (r->sync)
+    r->rc = bgv_sync_committee_put(r->c, r->id, r->seeds, r->active, r->n, (const uint8_t*)r->eff, r->n_eff,
+                                   r->max_incr, r->size, r->rounds, r->out, r->agg);
+  else if (r->electra)
+    r->rc = bgv_proposers_electra(r->c, r->seeds, r->n_seeds, r->active, r->n, (const uint16_t*)r->eff, r->n_eff,
+                                  r->max_incr, r->rounds, r->out);
   else
-    r->rc = bgv_proposers(r->c, r->seeds, r->n_seeds, r->active, r->n, r->eff, r->n_eff, r->max_incr, r->rounds,
-                          r->out);
+    r->rc = bgv_proposers(r->c, r->seeds, r->n_seeds, r->active, r->n, (const uint8_t*)r->eff, r->n_eff, r->max_incr,
+                          r->rounds, r->out);
 }
 
 static void samp_complete(napi_env env, napi_status status, void* data) {
@@ -552,24 +562,26 @@ static void samp_complete(napi_env env, napi_status status, void* data) {
 }
 
 /* argv[0] the context, then for sync [id, seed, active, eff, maxIncr, size, rounds], else
- * [seeds, active, eff, maxIncr, rounds] */
-static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
+ * [seeds, active, eff, maxIncr, rounds]; eff a Uint16Array when electra, else a Uint8Array */
+static napi_value samp_start(napi_env env, napi_callback_info info, int sync, int electra) {
   size_t argc = 8;
   napi_value argv[8], promise, name, ab, out, agg = NULL;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   OPEN_CTX(env, argv[0], ctx);
   const size_t a = sync ? 2 : 1; /* where the seeds are */
-  uint8_t *seeds, *act, *eff;
-  size_t seeds_len, act_len, eff_len;
+  uint8_t *seeds, *act;
+  void* eff;
+  size_t seeds_len, act_len, n_eff; /* n_eff counts elements: bytes, or uint16_t when electra */
   uint32_t id = 0, max_incr = 0, size = 0, rounds = 0;
   napi_typedarray_type act_type, eff_type;
   if (argc < (sync ? 8u : 6u) || (sync && napi_get_value_uint32(env, argv[1], &id) != napi_ok) ||
       get_bytes(env, argv[a], &seeds, &seeds_len) || seeds_len == 0 || seeds_len % 32 || (sync && seeds_len != 32) ||
       get_bytes(env, argv[a + 1], &act, &act_len) || act_len == 0 ||
       napi_get_typedarray_info(env, argv[a + 1], &act_type, NULL, NULL, NULL, NULL) != napi_ok ||
-      act_type != napi_uint32_array || get_bytes(env, argv[a + 2], &eff, &eff_len) || eff_len == 0 ||
-      napi_get_typedarray_info(env, argv[a + 2], &eff_type, NULL, NULL, NULL, NULL) != napi_ok ||
-      eff_type != napi_uint8_array || napi_get_value_uint32(env, argv[a + 3], &max_incr) != napi_ok ||
+      act_type != napi_uint32_array ||
+      napi_get_typedarray_info(env, argv[a + 2], &eff_type, &n_eff, &eff, NULL, NULL) != napi_ok || n_eff == 0 ||
+      eff_type != (electra ? napi_uint16_array : napi_uint8_array) ||
+      napi_get_value_uint32(env, argv[a + 3], &max_incr) != napi_ok ||
       (sync && napi_get_value_uint32(env, argv[a + 4], &size) != napi_ok) ||
       napi_get_value_uint32(env, argv[sync ? 7 : 5], &rounds) != napi_ok || (sync && (size < 1 || size > 65536)) ||
       seeds_len / 32 > 1024)
@@ -582,6 +594,7 @@ static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
   samp_req* r = (samp_req*)calloc(1, sizeof(samp_req));
   r->c = ctx;
   r->sync = sync;
+  r->electra = electra;
   r->id = id;
   r->n_seeds = (uint32_t)(seeds_len / 32);
   r->max_incr = max_incr;
@@ -591,7 +604,7 @@ static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
   r->active = (const uint32_t*)act;
   r->n = act_len / 4;
   r->eff = eff;
-  r->n_eff = eff_len;
+  r->n_eff = n_eff;
   r->out = (uint32_t*)dst;
   r->agg = (uint8_t*)agg_dst;
   if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
@@ -602,7 +615,7 @@ static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
       napi_create_reference(env, out, 1, &r->out_ref) != napi_ok ||
       (sync && napi_create_reference(env, agg, 1, &r->agg_ref) != napi_ok) ||
       napi_create_string_utf8(env, sync ? "blsgpu.syncCommitteePut" : "blsgpu.proposers", NAPI_AUTO_LENGTH, &name) !=
-          napi_ok ||
+          napi_ok || /* one resource name for both rules */
       napi_create_async_work(env, NULL, name, samp_execute, samp_complete, r, &r->work) != napi_ok ||
       napi_queue_async_work(env, r->work) != napi_ok) {
     napi_throw_error(env, NULL, "blsgpu: N-API failure");
@@ -611,8 +624,12 @@ static napi_value samp_start(napi_env env, napi_callback_info info, int sync) {
   return promise;
 }
 
-static napi_value js_proposers(napi_env env, napi_callback_info info) { return samp_start(env, info, 0); }
-static napi_value js_sync_committee_put(napi_env env, napi_callback_info info) { return samp_start(env, info, 1); }
+static napi_value js_proposers(napi_env env, napi_callback_info info) { return samp_start(env, info, 0, 0); }
+static napi_value js_sync_committee_put(napi_env env, napi_callback_info info) { return samp_start(env, info, 1, 0); }
+static napi_value js_proposers_electra(napi_env env, napi_callback_info info) { return samp_start(env, info, 0, 1); }
+static napi_value js_sync_committee_put_electra(napi_env env, napi_callback_info info) {
+  return samp_start(env, info, 1, 1);
+}
 
 /* aggregateCommitteeBits(ctx, id, bits: Uint8Array, nBits) -> Uint8Array(96): the aggregate of the
  * committee members whose bit is set, through the verify path's kernel (parity hook). */
@@ -1047,6 +1064,8 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"shufflingPut", NULL, js_shuffling_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"proposers", NULL, js_proposers, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"syncCommitteePut", NULL, js_sync_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"proposersElectra", NULL, js_proposers_electra, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"syncCommitteePutElectra", NULL, js_sync_committee_put_electra, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregateCommitteeBits", NULL, js_aggregate_committee_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"hashToG2", NULL, js_hash_to_g2, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"pubkeysValidate", NULL, js_pubkeys_validate, NULL, NULL, NULL, METHOD_ATTR, NULL},

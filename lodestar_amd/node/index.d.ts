@@ -87,6 +87,8 @@ export interface BlsGpuVerifierModules {
   metrics?: unknown | null;
 }
 
+/** the acceptance rule of balance-weighted sampling: one random byte ("phase0", the default) or 16 bits (EIP-7251) */
+export type SamplingRule = "phase0" | "electra";
 export declare class QueueError extends Error {
   type: {code: string};
 }
@@ -118,25 +120,28 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   ): Promise<Uint32Array>;
   /**
    * computeProposers on the device: the proposers of opts.slots slots from startSlot on, -1 where
-   * every candidate was rejected; the per-slot seeds are hashed here
+   * every candidate was rejected; the per-slot seeds are hashed here.  opts.rule "electra" selects
+   * EIP-7251's 16-bit draws: effectiveBalanceIncrements is then a Uint16Array or a number array (a
+   * Uint8Array is widened) and maxEffectiveBalanceIncrement may reach 65535 (mainnet: 2048)
    */
   computeProposers(
     epochSeed: Uint8Array,
     startSlot: number,
     activeIndices: Uint32Array | number[],
-    effectiveBalanceIncrements: Uint8Array,
-    opts: {slots: number; maxEffectiveBalanceIncrement: number; rounds: number}
+    effectiveBalanceIncrements: Uint8Array | Uint16Array | number[],
+    opts: {slots: number; maxEffectiveBalanceIncrement: number; rounds: number; rule?: SamplingRule}
   ): Promise<number[]>;
   /**
    * getNextSyncCommittee on the device: the first opts.size candidates accepted by balance (repeats
-   * kept) become committee id; resolves to the list and its 48-byte aggregate pubkey
+   * kept) become committee id; resolves to the list and its 48-byte aggregate pubkey.  opts.rule as
+   * for computeProposers
    */
   syncCommitteePut(
     id: number,
     seed: Uint8Array,
     activeIndices: Uint32Array | number[],
-    effectiveBalanceIncrements: Uint8Array,
-    opts: {size: number; maxEffectiveBalanceIncrement: number; rounds: number}
+    effectiveBalanceIncrements: Uint8Array | Uint16Array | number[],
+    opts: {size: number; maxEffectiveBalanceIncrement: number; rounds: number; rule?: SamplingRule}
   ): Promise<{indices: Uint32Array; aggregatePubkey: Uint8Array}>;
   /** drops the live ids of firstId .. firstId + count - 1; returns how many there were */
   committeeDropRange(firstId: number, count: number): number;
