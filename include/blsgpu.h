@@ -395,6 +395,50 @@ int bgv_pubkeys_validate(bgv_ctx* ctx, const uint8_t* keys48, size_t n, int32_t*
 int bgv_aggregate_signatures(bgv_ctx* ctx, const uint8_t* sigs96, const uint32_t* lens, const uint32_t* counts,
                              size_t naggs, uint8_t* out96, int32_t* out_status);
 
+/* Verify and aggregate: bgv_verify_spans whose call also returns, per caller-chosen pool key, the
+ * compressed sum of the signatures it accepted.  Replaces the gossip handlers' pair of steps
+ * (network/gossip/handlers/index.ts:199,285): verifySignatureSets([set], {batchable: true}), then
+ * on the main thread Signature.aggregate([aggregate.signature, Signature.fromBytes(sig, undefined,
+ * true)]) in the op pool (chain/opPools/attestationPool.ts:184-187,
+ * syncCommitteeMessagePool.ts:126-129), which decodes and subgroup-checks every signature a second
+ * time.  Here the verdict pass has proved membership, so the second decoding is the square root
+ * alone.
+ *   out_job_codes    exactly those of bgv_verify_spans on the same arguments (spans may be NULL)
+ *   agg_of_set[i]    the aggregate set i belongs to (< naggs), or BGV_NO_AGG
+ * Set i is accepted iff the code of the job that holds it is 1.  Aggregate a is the G2 sum of the
+ * signatures of the accepted sets with agg_of_set[i] == a, whatever their order or spacing; a
+ * repeated signature counts again, an infinity signature adds nothing and is counted.
+ *   out_agg_count[a]   how many sets were summed
+ *   out_agg_status[a]  0, -BGV_E_EMPTY_AGGREGATE when the count is 0, or -code when an accepted
+ *                      signature no longer decodes (the caller changed the buffer)
+ *   out_agg96[a]       the compressed sum, byte for byte bgv_aggregate_signatures' over the same
+ *                      signatures (the infinity encoding for a sum at infinity); zero when the
+ *                      status is not 0
+ * -BGV_E_ARG, nothing run and no output written: an agg_of_set[i] that is neither BGV_NO_AGG nor
+ * < naggs, naggs > 2^20, a null pointer that is needed.  naggs == 0 is bgv_verify_spans.
+ * When the call fails (a negative return) the aggregate outputs are not written.
+ * The signatures are read from sets[i].sig once the codes are final: the caller keeps them alive
+ * and unchanged until the call returns (until done() in the asynchronous form, which fires on a
+ * worker thread of the context after the aggregates are written; bgv_close ends a call whose
+ * aggregation is still queued with -BGV_E_CLOSED).
+ * Calls with at most BGV_SIGAGG_WAVE_MAX accepted signatures decode one signature per wavefront,
+ * larger ones one per lane. */
+#define BGV_NO_AGG 0xFFFFFFFFu
+#define BGV_SIGAGG_WAVE_MAX 2048
+int bgv_verify_aggregate(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                         const bgv_pkspan* spans, int mode, const uint32_t* agg_of_set, size_t naggs,
+                         int32_t* out_job_codes, uint8_t* out_agg96, int32_t* out_agg_status, uint32_t* out_agg_count,
+                         bgv_stats* stats);
+int bgv_verify_aggregate_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                               const bgv_pkspan* spans, int mode, const uint32_t* agg_of_set, size_t naggs,
+                               int32_t* out_job_codes, uint8_t* out_agg96, int32_t* out_agg_status,
+                               uint32_t* out_agg_count, bgv_stats* stats, bgv_done_fn done, void* user);
+
+/* Parity hook (tests only): how many aggregation steps of bgv_verify_aggregate calls on this context
+ * have launched the one-signature-per-wavefront decoding (out[0]) and the one-per-lane decoding
+ * (out[1]); a call that accepted nothing launches neither. */
+int bgv_debug_sigagg_launches(bgv_ctx* ctx, uint64_t out[2]);
+
 /* Deposit signature check (processDeposit.ts:62-70): key validated as above, then
  * Signature.fromBytes(sig, affine, true).verify(pk, signingRoot); any BLS error counts
  * as invalid.  out_valid[i] = 1 or 0. */

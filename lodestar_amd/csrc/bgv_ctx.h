@@ -156,6 +156,22 @@ struct FinalScratch {
   size_t cap = 0;
 };
 
+// bgv_verify_aggregate's aggregation step (bgv_sigagg.cpp; under util_mu): the accepted
+// signatures in member order, their points and statuses, per aggregate {first, count} and the
+// compressed sums, with the pinned staging of each.  Grown to the largest call seen.
+struct SigAggScratch {
+  uint8_t* d_sigs = nullptr;  // sig_cap x 96
+  void* d_pts = nullptr;      // sig_cap x bgv_g2_point_bytes()
+  int32_t* d_st = nullptr;    // sig_cap
+  size_t sig_cap = 0;
+  uint32_t* d_fc = nullptr;  // first[agg_cap], count[agg_cap]
+  uint8_t* d_out = nullptr;  // agg_cap x 96
+  size_t agg_cap = 0;
+  Pinned<uint8_t> h_sigs, h_out;
+  Pinned<int32_t> h_st;
+  Pinned<uint32_t> h_fc;
+};
+
 // Device-resident committees (bgv_committee_put).  Every device keeps a directory of
 // kComHandles entries (bgv_dcommittee: where the members are, how many, their pubkey sum) and one
 // pool of member indices; a committee has the same handle and pool range on every device.  The
@@ -231,6 +247,7 @@ struct CommitteeRec {
 };
 
 struct Call;
+struct SigAggTask;
 // What a super-batch's retry rounds need from its first pass.
 struct BatchState {
   std::chrono::steady_clock::time_point tb;
@@ -278,6 +295,7 @@ struct Device {
   uint32_t* com_list = nullptr;       // kComHandles words: the handles of one k_committee_total launch
   uint32_t* shuf_buf = nullptr;       // bgv_shuffling_put's scratch (active indices, digest table, pivots)
   size_t shuf_cap = 0;                // in words; grown on demand, under util_mu
+  SigAggScratch sigagg;               // device 0 only
   std::vector<Exec*> execs;
   // held while one super-batch runs its per-set kernels (pointer: Device stays movable)
   std::unique_ptr<std::mutex> compute_mu = std::make_unique<std::mutex>();
@@ -349,6 +367,15 @@ struct bgv_ctx {
   std::condition_variable split_cv;
   double kernel_ms[BGV_NKERNELS] = {};
   uint64_t kernel_launches = 0;
+  // bgv_verify_aggregate_async: calls whose codes are final and whose aggregation waits for the
+  // context's aggregation worker (started by the first such call; bgv_sigagg.cpp)
+  std::mutex agg_mu;
+  std::condition_variable agg_cv;
+  std::deque<SigAggTask*> agg_q;
+  std::thread agg_worker;
+  bool agg_stop = false;
+  // aggregation steps launched with the wavefront form [0] and the lane form [1] (bgv_debug_sigagg_launches)
+  std::atomic<uint64_t> sigagg_launches[2] = {};
   // dispatch
   std::vector<std::thread> dispatchers;
   std::mutex qmu;
@@ -400,5 +427,8 @@ bgv_dev_batch make_batch(Device& d, Exec& x, uint32_t nslots, uint32_t ngroups);
 int host_job_code(bgv_ctx* c, const bgv_job& jb, const bgv_set* sets, int32_t* code, PkForm pk = PkForm(),
                   Call* call = nullptr);
 void fp12_one_bytes(uint8_t out[576]);
+// bgv_sigagg.cpp
+void sigagg_stop(bgv_ctx* c);   // bgv_close: queued aggregations end with -BGV_E_CLOSED, the worker is joined
+void sigagg_free(Device& d);    // ctx_free_devices
 
 #pragma GCC visibility pop

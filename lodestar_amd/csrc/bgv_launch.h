@@ -168,6 +168,13 @@ hipError_t bgv_launch_sig_aggregate(const uint8_t* sigs96, const uint32_t* lens,
                                     const uint32_t* count, uint32_t naggs, void* pts, int32_t* status,
                                     uint8_t* out96, hipStream_t st);
 size_t bgv_g2_point_bytes();
+// bgv_verify_aggregate's aggregation step (bgv_k_sigagg.hip): the n accepted signatures (member
+// order, membership proved by the verdict pass) decompressed without a subgroup check into pts /
+// status -- one per wavefront (wave) or one per lane -- then one wavefront per aggregate sums
+// pts[first[a] .. first[a] + count[a]) into out96[a], compressed.
+hipError_t bgv_launch_sigagg(const uint8_t* sigs96, uint32_t n, bool wave, const uint32_t* first,
+                             const uint32_t* count, uint32_t naggs, void* pts, int32_t* status, uint8_t* out96,
+                             hipStream_t st);
 size_t bgv_fp12_bytes();
 hipError_t bgv_launch_fp12_bytes(const fp12_t* in, uint32_t n, uint8_t* out576, hipStream_t st);  // parity hooks
 hipError_t bgv_launch_partial(const bgv_dev_batch& b, uint32_t g0, uint32_t ng, void* scratch, uint8_t* out576,

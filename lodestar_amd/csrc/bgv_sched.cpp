@@ -866,6 +866,7 @@ static void ctx_free_devices(bgv_ctx* c) {
         if (q) (void)hipFree(q);
       d.shuf_buf = nullptr;
       d.shuf_cap = 0;
+      sigagg_free(d);
       d.com_dir = nullptr;
       d.com_pool = nullptr;
       d.com_list = nullptr;
@@ -972,6 +973,8 @@ int bgv_close(bgv_ctx* c) {
       if (t.joinable()) t.join();
     d.sched->retry_threads.clear();
   }
+  // every verify call has finished: what still waits for its aggregation ends here
+  sigagg_stop(c);
   std::unique_lock<std::shared_mutex> lk(c->cache_mu);
   if (c->closed.exchange(true)) return BGV_OK;
   ctx_free_devices(c);

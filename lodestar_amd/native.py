@@ -38,6 +38,8 @@ MAX_COMMITTEES = 16384
 NO_COMMITTEE = 0xFFFFFFFF
 NO_PROPOSER = 0xFFFFFFFF
 SAMPLE_MAX_TRIES = 65536
+NO_AGG = 0xFFFFFFFF
+SIGAGG_WAVE_MAX = 2048  # BGV_SIGAGG_WAVE_MAX of include/blsgpu.h
 
 EXPORTED_SYMBOLS = [
     "bgv_init", "bgv_close", "bgv_destroy", "bgv_pubkeys_put", "bgv_pubkeys_count", "bgv_verify",
@@ -49,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "bgv_aggregate_committee_bits", "bgv_shuffling_put", "bgv_committee_drop_range",
     "bgv_proposers", "bgv_sync_committee_put", "bgv_proposers_electra", "bgv_sync_committee_put_electra",
     "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
+    "bgv_verify_aggregate", "bgv_verify_aggregate_async", "bgv_debug_sigagg_launches",
 ]
 
 
@@ -145,6 +148,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_verify_spans": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P], ctypes.c_int),
             "bgv_verify_spans_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, DONE_FN, P], ctypes.c_int),
             "bgv_aggregate_span": ([P, P, P], ctypes.c_int),
+            "bgv_verify_aggregate": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, SZ, P, P, P, P, P], ctypes.c_int),
+            "bgv_debug_sigagg_launches": ([P, P], ctypes.c_int),
+            "bgv_verify_aggregate_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, SZ, P, P, P, P, P, DONE_FN, P],
+                                           ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
@@ -152,7 +159,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                         "bgv_aggregate_committee_bits", "bgv_shuffling_put",
                         "bgv_committee_drop_range", "bgv_proposers", "bgv_sync_committee_put",
                         "bgv_proposers_electra", "bgv_sync_committee_put_electra",
-                        "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
+                        "bgv_verify_aggregate", "bgv_verify_aggregate_async",
+                        "bgv_debug_sigagg_launches") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -499,6 +508,75 @@ class Context:
         _check(rc)
         return list(out[:njobs])
 
+    def verify_aggregate(self, jobs, agg_of_set: Sequence[int], naggs: int, mode: int = MODE_WORKER,
+                         stats: Optional[BgvStats] = None):
+        """bgv_verify_aggregate: verify_jobs whose call also sums the signatures it accepted.
+        agg_of_set[i] is the aggregate of set i (in job order; < naggs) or NO_AGG.  Returns
+        (codes, [(status, count, compressed96)])."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(agg_of_set) != packed.nsets:
+            raise ValueError("agg_of_set takes one entry per set")
+        njobs = len(packed.jobs_in)
+        out = (ctypes.c_int32 * max(1, njobs))()
+        tags = (ctypes.c_uint32 * max(1, packed.nsets))(*agg_of_set)
+        agg = ctypes.create_string_buffer(96 * max(1, naggs))
+        ast = (ctypes.c_int32 * max(1, naggs))()
+        cnt = (ctypes.c_uint32 * max(1, naggs))()
+        st = ctypes.byref(stats) if stats is not None else None
+        _check(self.lib.bgv_verify_aggregate(self._h, packed.jobs, njobs, packed.sets, packed.nsets,
+                                             packed.as_spans(), mode, tags, naggs, out, agg, ast, cnt, st))
+        return list(out[:njobs]), [(ast[a], cnt[a], agg.raw[96 * a:96 * a + 96]) for a in range(naggs)]
+
+    def sigagg_launches(self):
+        """bgv_debug_sigagg_launches (parity hook): aggregation steps launched so far with the
+        (wavefront, lane) decoding form."""
+        out = (ctypes.c_uint64 * 2)()
+        _check(self.lib.bgv_debug_sigagg_launches(self._h, out))
+        return out[0], out[1]
+
+    def verify_aggregate_async(self, jobs, agg_of_set: Sequence[int], naggs: int, mode: int = MODE_WORKER):
+        """bgv_verify_aggregate_async: returns a PendingAggregate whose wait() gives what
+        verify_aggregate returns, as the outputs stood when done() fired."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(agg_of_set) != packed.nsets:
+            raise ValueError("agg_of_set takes one entry per set")
+        return PendingAggregate(self, packed, agg_of_set, naggs, mode)
+
+
+class PendingAggregate:
+    """One bgv_verify_aggregate_async call: keeps its buffers alive until done() has fired on the
+    context's worker thread, where the outputs are read."""
+
+    def __init__(self, ctx: "Context", packed: "PackedCall", agg_of_set: Sequence[int], naggs: int, mode: int):
+        self._packed = packed
+        njobs = len(packed.jobs_in)
+        self._out = (ctypes.c_int32 * max(1, njobs))()
+        self._tags = (ctypes.c_uint32 * max(1, packed.nsets))(*agg_of_set)
+        self._agg = ctypes.create_string_buffer(96 * max(1, naggs))
+        self._ast = (ctypes.c_int32 * max(1, naggs))()
+        self._cnt = (ctypes.c_uint32 * max(1, naggs))()
+        self.stats = BgvStats()
+        self._event = threading.Event()
+        self._rc = None
+        self._result = None
+
+        def done(_user, rc):
+            self._rc = rc
+            self._result = (list(self._out[:njobs]),
+                            [(self._ast[a], self._cnt[a], self._agg.raw[96 * a:96 * a + 96]) for a in range(naggs)])
+            self._event.set()
+
+        self._done = DONE_FN(done)
+        _check(ctx.lib.bgv_verify_aggregate_async(ctx.handle, packed.jobs, njobs, packed.sets, packed.nsets,
+                                                  packed.as_spans(), mode, self._tags, naggs, self._out, self._agg,
+                                                  self._ast, self._cnt, ctypes.byref(self.stats), self._done, None))
+
+    def wait(self, timeout: Optional[float] = None):
+        if not self._event.wait(timeout):
+            raise TimeoutError("bgv_verify_aggregate_async: done() has not fired")
+        _check(self._rc)
+        return self._result
+
 
 class SetSpec:
     """One ISignatureSet in C-ABI terms: pubkeys by cache index, as 96-B bytes, or as the members
@@ -574,6 +652,24 @@ class PackedSingleSets:
 
 class PackedCall:
     """Keeps every buffer of one bgv_verify call alive and builds the C arrays."""
+
+    def as_spans(self):
+        """The call's bgv_pkspan array (None for plain sets): a (committee, bitfield) set is the
+        span over that one committee."""
+        if self.spans is not None or self.pkbits is None:
+            return self.spans
+        spans = (BgvPkSpan * max(1, self.nsets))()  # zeroed: n_committees = 0
+        for i in range(self.nsets):
+            if self.pkbits[i].committee == NO_COMMITTEE:
+                continue
+            one = (ctypes.c_uint32 * 1)(self.pkbits[i].committee)
+            self._keep.append(one)
+            spans[i].committees = ctypes.addressof(one)
+            spans[i].n_committees = 1
+            spans[i].n_bits = self.pkbits[i].n_bits
+            spans[i].bits = self.pkbits[i].bits
+        self.spans = spans
+        return spans
 
     def __init__(self, jobs):
         all_sets = []

@@ -34,6 +34,9 @@ const MAX_SIGNATURE_SETS_PER_JOB = 128; // index.ts:39
 // the later device chain, profiles/r03/gossip/two_wave_miller.jsonl).
 const MAX_BUFFERED_SIGS = 63;
 const MAX_BUFFER_WAIT_MS = 1;
+// canAcceptWork() turns false while this many sets are queued or in flight: one default
+// super-batch (131,072 sets) running and one forming.  A default, not a tuned number.
+const MAX_INFLIGHT_SIGS = 262144;
 
 // committee: not in the reference -- an aggregate as the beacon node holds it before
 // bits.intersectValues(committeeIndices): a committee stored on the device (committeePut) and
@@ -169,6 +172,8 @@ class BlsGpuVerifier {
     this.blsVerifyAllMultiThread = opts.blsVerifyAllMultiThread || false;
     this.maxBufferedSigs = opts.maxBufferedSigs || MAX_BUFFERED_SIGS;
     this.maxBufferWaitMs = opts.maxBufferWaitMs || MAX_BUFFER_WAIT_MS;
+    this.maxInflightSigs = opts.maxInflightSigs || MAX_INFLIGHT_SIGS;
+    this.inflightSigs = 0; // sets queued, buffered or in a device call
     this.jobs = [];
     this.bufferedJobs = null;
     this.closed = false;
@@ -270,10 +275,12 @@ class BlsGpuVerifier {
     if (opts.verifyOnMainThread && !this.blsVerifyAllMultiThread) {
       // index.ts:138-151: one job verified at once (no buffering)
       const timer = this.metrics ? this.metrics.blsThreadPool.mainThreadDurationInThreadPool.startTimer() : null;
+      this.inflightSigs += sets.length;
       try {
         const codes = await addon.verify(this.ctx, [{sets: sets.map(toNativeSet), batchable: false}], 1);
         return unwrap(codes[0]);
       } finally {
+        this.inflightSigs -= sets.length;
         if (timer) timer();
       }
     }
@@ -284,6 +291,45 @@ class BlsGpuVerifier {
     );
     if (results.length === 0) throw Error("Empty results array");
     return results.every((v) => v === true);
+  }
+
+  /**
+   * IBlsVerifier.verifySignatureSetsSameMessage (chain/bls/interface.ts, from Electra-era
+   * versions on): sets of {publicKey, signature} over one signing root, e.g. the unaggregated
+   * attestations of one AttestationData.  Every set is its own batchable one-set job over the
+   * shared root, so one bad signature costs the others nothing; resolves to one boolean per set.
+   * A set whose job ends in an error code (an undecodable signature, an unknown index) is false,
+   * as the interface's per-set retry reports it; only a failed call (a closed verifier, a device
+   * error) rejects.
+   */
+  async verifySignatureSetsSameMessage(sets, message, opts = {}) {
+    return (await this._sameMessage(sets, message, opts, false)).results;
+  }
+
+  /**
+   * verifySignatureSetsSameMessage whose device call also sums the signatures it accepted
+   * (bgv_verify_aggregate): resolves to {results, signature}, signature the compressed aggregate
+   * of the sets whose result is true -- what the op pool's Signature.aggregate would compute after
+   * decoding and subgroup-checking each one again (opPools/attestationPool.ts:184-187,
+   * syncCommitteeMessagePool.ts:126-129) -- or null when no set was accepted.
+   */
+  async verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    return this._sameMessage(sets, message, opts, true);
+  }
+
+  async _sameMessage(sets, message, opts, aggregate) {
+    if (this.pendingRuns.length || this.flushing) await this.flushPubkeys();
+    if (sets.length === 0) return {results: [], signature: null};
+    const native = sets.map((s) =>
+      toNativeSet({type: SignatureSetType.single, pubkey: s.publicKey, signingRoot: message, signature: s.signature})
+    );
+    // one unit in the buffer and one device call, whatever its size; each set its own job there
+    return this.queueBlsWork({opts: {...opts, batchable: true}, sets: native, perSet: true, aggregate});
+  }
+
+  /** IBlsVerifier.canAcceptWork: false while the sets queued or in flight reach opts.maxInflightSigs. */
+  canAcceptWork() {
+    return !this.closed && this.inflightSigs < this.maxInflightSigs;
   }
 
   /**
@@ -366,7 +412,10 @@ class BlsGpuVerifier {
     if (this.closed) return;
     if (this.bufferedJobs) clearTimeout(this.bufferedJobs.timeout);
     const pending = this.jobs.concat(this.bufferedJobs ? this.bufferedJobs.jobs : []);
-    for (const job of pending) job.reject(new QueueError("QUEUE_ABORTED"));
+    for (const job of pending) {
+      this.inflightSigs -= job.workReq.sets.length;
+      job.reject(new QueueError("QUEUE_ABORTED"));
+    }
     this.jobs = [];
     this.bufferedJobs = null;
     this.closed = true;
@@ -377,6 +426,7 @@ class BlsGpuVerifier {
     if (this.closed) return Promise.reject(new QueueError("QUEUE_ABORTED"));
     return new Promise((resolve, reject) => {
       const job = {resolve, reject, workReq, addedTimeMs: Date.now()};
+      this.inflightSigs += workReq.sets.length;
       if (workReq.opts.batchable) {
         if (!this.bufferedJobs) {
           this.bufferedJobs = {jobs: [], sigCount: 0, timeout: setTimeout(this.runBufferedJobs, this.maxBufferWaitMs)};
@@ -421,16 +471,44 @@ class BlsGpuVerifier {
       m.totalJobsStarted.inc(jobs.length);
       m.totalSigSetsStarted.inc(startedSigSets);
     }
+    // A same-message caller's sets travel as one-set jobs from `first` on; with an aggregate
+    // wanted they carry an id of their own within this call.  Without a tagged set the call is
+    // addon.verify, exactly as before.
+    const nativeJobs = [];
+    let naggs = 0;
+    for (const job of jobs) {
+      const w = job.workReq;
+      job.first = nativeJobs.length;
+      if (!w.perSet) {
+        nativeJobs.push({sets: w.sets, batchable: Boolean(w.opts.batchable)});
+        continue;
+      }
+      job.agg = w.aggregate ? naggs++ : -1;
+      for (const s of w.sets) nativeJobs.push({sets: [job.agg < 0 ? s : {...s, agg: job.agg}], batchable: true});
+    }
     try {
-      const codes = await addon.verify(
-        this.ctx,
-        jobs.map((j) => ({sets: j.workReq.sets, batchable: Boolean(j.workReq.opts.batchable)})),
-        0
-      );
+      let codes, aggs;
+      if (naggs) {
+        const res = await addon.verifyAggregate(this.ctx, nativeJobs, 0);
+        codes = res.codes;
+        codes.stats = res.stats;
+        aggs = res.aggs;
+      } else {
+        codes = await addon.verify(this.ctx, nativeJobs, 0);
+      }
       let successCount = 0;
       let errorCount = 0;
-      jobs.forEach((job, i) => {
-        const c = codes[i];
+      jobs.forEach((job) => {
+        const w = job.workReq;
+        if (w.perSet) {
+          // per set: an error code is false for that set (the interface's per-set retry), never a rejection
+          const results = w.sets.map((_, k) => codes[job.first + k] === 1);
+          w.sets.forEach((_, k) => (codes[job.first + k] < 0 ? errorCount++ : successCount++));
+          const ok = job.agg >= 0 && aggs.status[job.agg] === 0;
+          job.resolve({results, signature: ok ? aggs.sigs.slice(96 * job.agg, 96 * job.agg + 96) : null});
+          return;
+        }
+        const c = codes[job.first];
         if (c < 0) {
           errorCount += job.workReq.sets.length;
           job.reject(Error(addon.strerror(-c)));
@@ -454,6 +532,8 @@ class BlsGpuVerifier {
       }
     } catch (e) {
       for (const job of jobs) job.reject(e);
+    } finally {
+      this.inflightSigs -= startedSigSets;
     }
   };
 

@@ -120,6 +120,13 @@ typedef struct {
   napi_deferred deferred;
   napi_ref* refs; /* keep every input buffer alive until completion */
   size_t nrefs;
+  /* verifyAggregate: the sets' `agg` tags beside sets, and the aggregates' outputs */
+  int aggregate;
+  uint32_t* tags;
+  size_t naggs;
+  uint8_t* agg96;
+  int32_t* agg_status;
+  uint32_t* agg_count;
 } verify_req;
 
 static void verify_call_js(napi_env env, napi_value js_cb, void* context, void* data);
@@ -783,16 +790,24 @@ static napi_value js_deposits_verify(napi_env env, napi_callback_info info) {
 }
 
 /* ---- verify: bgv_verify_async + threadsafe completion + Promise ----------- */
-static void free_req(napi_env env, verify_req* r) {
-  for (size_t i = 0; i < r->nrefs; ++i) napi_delete_reference(env, r->refs[i]);
-  if (r->ctx_ref) napi_delete_reference(env, r->ctx_ref);
+static void free_req_heap(verify_req* r) {
   free(r->refs);
   free(r->jobs);
   free(r->sets);
   free(r->pkbits);
   free(r->spans);
   free(r->codes);
+  free(r->tags);
+  free(r->agg96);
+  free(r->agg_status);
+  free(r->agg_count);
   free(r);
+}
+
+static void free_req(napi_env env, verify_req* r) {
+  for (size_t i = 0; i < r->nrefs; ++i) napi_delete_reference(env, r->refs[i]);
+  if (r->ctx_ref) napi_delete_reference(env, r->ctx_ref);
+  free_req_heap(r);
 }
 
 static void settle(napi_env env, verify_req* r) {
@@ -824,7 +839,29 @@ static void settle(napi_env env, verify_req* r) {
   napi_create_double(env, r->stats.wall_ms, &v);
   napi_set_named_property(env, st, "wallMs", v);
   napi_set_named_property(env, arr, "stats", st);
-  napi_resolve_deferred(env, r->deferred, arr);
+  if (!r->aggregate) {
+    napi_resolve_deferred(env, r->deferred, arr);
+    return;
+  }
+  /* verifyAggregate: {codes, stats, aggs: {status, count, sigs}} */
+  napi_value res, aggs, sab, sarr, cab, carr, sigs;
+  napi_create_object(env, &res);
+  napi_set_named_property(env, res, "codes", arr);
+  napi_set_named_property(env, res, "stats", st);
+  napi_create_object(env, &aggs);
+  napi_create_arraybuffer(env, 4 * r->naggs, &dst, &sab);
+  memcpy(dst, r->agg_status, 4 * r->naggs);
+  napi_create_typedarray(env, napi_int32_array, r->naggs, sab, 0, &sarr);
+  napi_set_named_property(env, aggs, "status", sarr);
+  napi_create_arraybuffer(env, 4 * r->naggs, &dst, &cab);
+  memcpy(dst, r->agg_count, 4 * r->naggs);
+  napi_create_typedarray(env, napi_uint32_array, r->naggs, cab, 0, &carr);
+  napi_set_named_property(env, aggs, "count", carr);
+  sigs = new_bytes(env, 96 * r->naggs, &dst);
+  memcpy(dst, r->agg96, 96 * r->naggs);
+  napi_set_named_property(env, aggs, "sigs", sigs);
+  napi_set_named_property(env, res, "aggs", aggs);
+  napi_resolve_deferred(env, r->deferred, res);
 }
 
 /* main thread: a verify finished on a dispatcher thread */
@@ -840,13 +877,7 @@ static void verify_call_js(napi_env env, napi_value js_cb, void* context, void* 
   } else {
     /* environment teardown drained the queue: no JS to settle (the promise dies with the
      * environment) and no env for the references (they die with it too); free the heap part */
-    free(r->refs);
-    free(r->jobs);
-    free(r->sets);
-    free(r->pkbits);
-    free(r->spans);
-    free(r->codes);
-    free(r);
+    free_req_heap(r);
   }
 }
 
@@ -883,7 +914,11 @@ static void addon_finalize(napi_env env, void* data, void* hint) {
   addon_unref(a);
 }
 
-static napi_value js_verify(napi_env env, napi_callback_info info) {
+/* verify(ctx, jobs, mode) resolves to the codes (an Int32Array with .stats); verifyAggregate(ctx,
+ * jobs, mode), whose sets may carry `agg: number` (the aggregate the set's signature joins when its
+ * job is accepted; bgv_verify_aggregate), to {codes, stats, aggs: {status, count, sigs}} with one
+ * entry per aggregate 0 .. the largest agg given */
+static napi_value verify_start(napi_env env, napi_callback_info info, int aggregate) {
   size_t argc = 3;
   napi_value argv[3];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -899,6 +934,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   }
   verify_req* r = (verify_req*)calloc(1, sizeof(verify_req));
   r->actx = a;
+  r->aggregate = aggregate;
   int32_t mode = 0;
   if (argc >= 3) napi_get_value_int32(env, argv[2], &mode);
   r->mode = mode;
@@ -911,6 +947,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   r->sets = (bgv_set*)calloc(cap, sizeof(bgv_set));
   r->pkbits = (bgv_pkbits*)calloc(cap, sizeof(bgv_pkbits));
   r->spans = (bgv_pkspan*)calloc(cap, sizeof(bgv_pkspan));
+  r->tags = (uint32_t*)calloc(cap, sizeof(uint32_t));
   size_t refcap = 256;
   r->refs = (napi_ref*)calloc(refcap, sizeof(napi_ref));
   for (uint32_t j = 0; j < njobs; ++j) {
@@ -931,6 +968,7 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
         r->sets = (bgv_set*)realloc(r->sets, cap * sizeof(bgv_set));
         r->pkbits = (bgv_pkbits*)realloc(r->pkbits, cap * sizeof(bgv_pkbits));
         r->spans = (bgv_pkspan*)realloc(r->spans, cap * sizeof(bgv_pkspan));
+        r->tags = (uint32_t*)realloc(r->tags, cap * sizeof(uint32_t));
       }
       if (r->nrefs + 4 > refcap) {
         refcap *= 2;
@@ -955,6 +993,20 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
       pb->n_bits = 0;
       pb->bits = NULL;
       memset(&r->spans[r->nsets], 0, sizeof(bgv_pkspan));
+      r->tags[r->nsets] = BGV_NO_AGG;
+      bool tagged = false;
+      if (aggregate) napi_has_named_property(env, s, "agg", &tagged);
+      if (tagged) {
+        napi_value av;
+        uint32_t tag = 0;
+        napi_get_named_property(env, s, "agg", &av);
+        if (napi_get_value_uint32(env, av, &tag) != napi_ok || tag >= (1u << 20)) {
+          free_req(env, r);
+          return throw_code(env, -BGV_E_ARG);
+        }
+        r->tags[r->nsets] = tag;
+        if ((size_t)tag + 1 > r->naggs) r->naggs = (size_t)tag + 1;
+      }
       bgv_set* st = &r->sets[r->nsets++];
       memset(st, 0, sizeof(*st));
       uint8_t *pkd, *md, *sd;
@@ -1022,7 +1074,12 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   CHECK(env, napi_create_reference(env, argv[0], 1, &r->ctx_ref));
   if (a->inflight++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
   int rc;
-  if (r->any_span) { /* the one-committee sets of the call as spans of one committee */
+  if (aggregate) {
+    r->agg96 = (uint8_t*)calloc(r->naggs ? r->naggs : 1, 96);
+    r->agg_status = (int32_t*)calloc(r->naggs ? r->naggs : 1, sizeof(int32_t));
+    r->agg_count = (uint32_t*)calloc(r->naggs ? r->naggs : 1, sizeof(uint32_t));
+  }
+  if (r->any_span || (aggregate && r->any_committee)) { /* the one-committee sets of the call as spans of one committee */
     for (size_t i = 0; i < r->nsets; ++i)
       if (r->pkbits[i].committee != BGV_NO_COMMITTEE) {
         r->spans[i].committees = &r->pkbits[i].committee;
@@ -1030,6 +1087,13 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
         r->spans[i].n_bits = r->pkbits[i].n_bits;
         r->spans[i].bits = r->pkbits[i].bits;
       }
+    r->any_span = 1;
+  }
+  if (aggregate) {
+    rc = bgv_verify_aggregate_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_span ? r->spans : NULL, r->mode,
+                                    r->tags, r->naggs, r->codes, r->agg96, r->agg_status, r->agg_count, &r->stats,
+                                    verify_done, r);
+  } else if (r->any_span) {
     rc = bgv_verify_spans_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->spans, r->mode, r->codes, &r->stats,
                                 verify_done, r);
   } else {
@@ -1045,6 +1109,9 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+static napi_value js_verify(napi_env env, napi_callback_info info) { return verify_start(env, info, 0); }
+static napi_value js_verify_aggregate(napi_env env, napi_callback_info info) { return verify_start(env, info, 1); }
+
 #define METHOD_ATTR ((napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable))
 
 static napi_value init_module(napi_env env, napi_value exports) {
@@ -1057,6 +1124,7 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"keygen", NULL, js_keygen, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"sign", NULL, js_sign, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"verify", NULL, js_verify, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"verifyAggregate", NULL, js_verify_aggregate, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregatePubkeys", NULL, js_aggregate_pubkeys, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeePut", NULL, js_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},

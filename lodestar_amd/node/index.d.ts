@@ -15,7 +15,14 @@ export interface VerifySignatureOpts {
 /** interface.ts:20-46 */
 export interface IBlsVerifier {
   verifySignatureSets(sets: ISignatureSet[], opts?: VerifySignatureOpts): Promise<boolean>;
+  /** one boolean per set; every set is verified on its own over the shared signing root */
+  verifySignatureSetsSameMessage(
+    sets: SameMessageSet[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<boolean[]>;
   close(): Promise<void>;
+  canAcceptWork(): boolean;
 }
 
 export declare const SignatureSetType: {
@@ -74,10 +81,18 @@ export type ISignatureSet =
   | ICommitteeSignatureSet
   | ICommitteesSignatureSet;
 
+/** one signer of a shared signing root (an unaggregated attestation, a sync committee message) */
+export interface SameMessageSet {
+  publicKey: PubkeyRef;
+  signature: Uint8Array; // 96 bytes compressed G2 (untrusted)
+}
+
 export interface BlsGpuVerifierOpts {
   devices?: number[];
   maxBufferedSigs?: number;
   maxBufferWaitMs?: number;
+  /** canAcceptWork() is false while this many sets are queued or in flight (default 262,144) */
+  maxInflightSigs?: number;
   blsVerifyAllMultiThread?: boolean;
   /** called once per uploaded run that held undecodable keys (those indices stay unusable) */
   onPubkeyError?: (e: Error, first: number, n: number) => void;
@@ -96,6 +111,22 @@ export declare class QueueError extends Error {
 export declare class BlsGpuVerifier implements IBlsVerifier {
   constructor(opts?: BlsGpuVerifierOpts, modules?: BlsGpuVerifierModules);
   verifySignatureSets(sets: ISignatureSet[], opts?: VerifySignatureOpts): Promise<boolean>;
+  verifySignatureSetsSameMessage(
+    sets: SameMessageSet[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<boolean[]>;
+  /**
+   * verifySignatureSetsSameMessage whose device call also returns the compressed sum of the
+   * accepted sets' signatures (null when none was accepted): the op pool's Signature.aggregate
+   * without a second decoding and subgroup check of each signature.
+   */
+  verifyAndAggregateSameMessage(
+    sets: SameMessageSet[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<{results: boolean[]; signature: Uint8Array | null}>;
+  canAcceptWork(): boolean;
   close(): Promise<void>;
   /** state-transition pubkey-added hook: (index, 48-byte pubkey, PublicKey?) */
   pubkeyAddedHook(): (index: number, pubkey: Uint8Array, pk?: object) => void;

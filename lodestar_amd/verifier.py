@@ -175,6 +175,44 @@ class BlsGpuVerifier:
                           pubkeys=list(public_keys))
         return await self.verify_signature_sets([s], VerifySignatureOpts(batchable=False))
 
+    async def verify_signature_sets_same_message(self, sets: Sequence[tuple], message: bytes,
+                                                 opts: Optional[VerifySignatureOpts] = None) -> List[bool]:
+        """IBlsVerifier.verifySignatureSetsSameMessage: sets of (public key, signature) over one
+        signing root, each verified as its own batchable one-set job in one device call.  One
+        bool per set; a set whose job ends in an error code is False, as the interface's per-set
+        retry reports it.  opts is taken for the interface's sake and not read: every set is a
+        batchable job whatever it says, and unlike the Node verifier's this call does not pass
+        through the buffer -- it is a device call of its own, at once."""
+        return (await self._same_message(sets, message, False))[0]
+
+    async def verify_and_aggregate_same_message(self, sets: Sequence[tuple], message: bytes,
+                                                opts: Optional[VerifySignatureOpts] = None):
+        """verify_signature_sets_same_message whose device call also sums the signatures it
+        accepted (bgv_verify_aggregate): (results, compressed aggregate or None when no set was
+        accepted).  opts and buffering as verify_signature_sets_same_message."""
+        return await self._same_message(sets, message, True)
+
+    async def _same_message(self, sets, message: bytes, aggregate: bool):
+        if self.closed:
+            raise QueueError("QUEUE_ABORTED")
+        if len(sets) == 0:
+            return [], None
+        jobs = [([to_set_spec(ISignatureSet(SignatureSetType.single, signing_root=message, signature=sig,
+                                            pubkey=pk))], True) for pk, sig in sets]
+        stats = native.BgvStats()
+
+        def call():
+            if not aggregate:
+                return self.ctx.verify_jobs(jobs, native.MODE_WORKER, stats), [(-native.BGV_E_EMPTY_AGGREGATE, 0, None)]
+            return self.ctx.verify_aggregate(jobs, [0] * len(jobs), 1, native.MODE_WORKER, stats)
+
+        codes, aggs = await asyncio.get_running_loop().run_in_executor(None, call)
+        self._account(stats)
+        self.metrics["error_sets"] += sum(1 for c in codes if c < 0)
+        self.metrics["success_sets"] += sum(1 for c in codes if c >= 0)
+        status, _, sig = aggs[0]
+        return [c == 1 for c in codes], sig if status == 0 else None
+
     async def close(self):
         if self.buffered and self.buffered.get("timer"):
             self.buffered["timer"].cancel()
