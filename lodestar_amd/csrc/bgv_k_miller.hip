@@ -464,6 +464,7 @@ hipError_t bgv_launch_miller(const bgv_dev_batch& b, const bgv_streams& s) {
   const uint32_t n = b.nslots;
   if (n == 0) return hipSuccess;
   if (bgv_sig_pairs(b)) {  // no group sums: every slot's own signature pair beside its set pair
+    BGV_MARK(2);  // both events of the pair on every route: prof_add measures from one to the other
     hipLaunchKernelGGL(k_miller_wide, dim3(2 * n), dim3(128), 0, s.main, b.slots, n, b.rpk, b.h, b.sig_status,
                        b.pk_status, b.f, n, b.gsum, b.gpair, b.rsig, b.fsig);
     BGV_MARK(3);

@@ -152,7 +152,12 @@ static void prof_add(bgv_ctx* c, Exec& x, bool sets, bool groups) {
     const bool is_set_kernel = k < BGV_NSETKERNELS;
     if ((is_set_kernel && !sets) || (!is_set_kernel && !groups)) continue;
     float km = 0;
-    if (hipEventElapsedTime(&km, x.kev[2 * k], x.kev[2 * k + 1]) == hipSuccess) c->kernel_ms[k] += km;
+    if (hipEventElapsedTime(&km, x.kev[2 * k], x.kev[2 * k + 1]) == hipSuccess)
+      c->kernel_ms[k] += km;
+    else
+      // A failed query stays this thread's last error, and the next launch check on the thread
+      // (hipGetLastError in bgv_launch_prep) would fail a later call with it.
+      (void)hipGetLastError();
   }
   if (sets) c->kernel_launches++;
 }

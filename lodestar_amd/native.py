@@ -508,6 +508,14 @@ class Context:
         _check(rc)
         return list(out[:njobs])
 
+    def verify_jobs_async(self, jobs, mode: int = MODE_WORKER) -> "PendingVerify":
+        """verify_jobs through the asynchronous entry point of the call's form (bgv_verify_async,
+        bgv_verify_bits_async or bgv_verify_spans_async): the call is queued when this returns, so
+        calls submitted from one thread are queued in that order.  Returns a PendingVerify whose
+        wait() gives what verify_jobs returns."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        return PendingVerify(self, packed, mode)
+
     def verify_aggregate(self, jobs, agg_of_set: Sequence[int], naggs: int, mode: int = MODE_WORKER,
                          stats: Optional[BgvStats] = None):
         """bgv_verify_aggregate: verify_jobs whose call also sums the signatures it accepted.
@@ -541,6 +549,46 @@ class Context:
         if len(agg_of_set) != packed.nsets:
             raise ValueError("agg_of_set takes one entry per set")
         return PendingAggregate(self, packed, agg_of_set, naggs, mode)
+
+
+class PendingVerify:
+    """One bgv_verify_async / bgv_verify_bits_async / bgv_verify_spans_async call: keeps its
+    buffers and its callback alive until done() has fired on one of the context's threads (or, for
+    a call the host's checks decide alone, inside the submit), where the codes are read.  `stats`
+    is the call's BgvStats, filled before done()."""
+
+    def __init__(self, ctx: "Context", packed: "PackedCall", mode: int):
+        self._packed = packed
+        njobs = len(packed.jobs_in)
+        self._out = (ctypes.c_int32 * max(1, njobs))()
+        self.stats = BgvStats()
+        self._event = threading.Event()
+        self._rc = None
+        self._result = None
+
+        def done(_user, rc):
+            self._rc = rc
+            self._result = list(self._out[:njobs])
+            self._event.set()
+
+        self._done = DONE_FN(done)
+        st = ctypes.byref(self.stats)
+        if packed.spans is not None:  # the entry point of the call's form, as verify_jobs picks it
+            rc = ctx.lib.bgv_verify_spans_async(ctx.handle, packed.jobs, njobs, packed.sets, packed.nsets,
+                                                packed.spans, mode, self._out, st, self._done, None)
+        elif packed.pkbits is not None:
+            rc = ctx.lib.bgv_verify_bits_async(ctx.handle, packed.jobs, njobs, packed.sets, packed.nsets,
+                                               packed.pkbits, mode, self._out, st, self._done, None)
+        else:
+            rc = ctx.lib.bgv_verify_async(ctx.handle, packed.jobs, njobs, packed.sets, packed.nsets, mode,
+                                          self._out, st, self._done, None)
+        _check(rc)
+
+    def wait(self, timeout: Optional[float] = None) -> List[int]:
+        if not self._event.wait(timeout):
+            raise TimeoutError("bgv_verify_async: done() has not fired")
+        _check(self._rc)
+        return self._result
 
 
 class PendingAggregate:
