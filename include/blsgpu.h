@@ -439,6 +439,74 @@ int bgv_verify_aggregate_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, 
  * (out[1]); a call that accepted nothing launches neither. */
 int bgv_debug_sigagg_launches(bgv_ctx* ctx, uint64_t out[2]);
 
+/* Device-resident signature pools: the op pools' running aggregate per (slot, data root), kept on
+ * device 0 and fed by verify calls.  Replaces, after every gossip verify call, the op pool's
+ * Signature.fromBytes of the 96 bytes bgv_verify_aggregate returned (an Fp2 square root on the main
+ * thread) and its Signature.aggregate([aggregate.signature, signature]) into the running aggregate
+ * (chain/opPools/attestationPool.ts:184-187, syncCommitteeMessagePool.ts:126-129), and the
+ * toBytes() of getAggregate: the node sends bytes, gets verdicts, and reads 96 bytes once, when an
+ * aggregator asks.  A pool entry is a G2 accumulator with a count; the caller chooses its id
+ * (0 .. BGV_MAX_SIGPOOL - 1).
+ *
+ * bgv_sigpool_open: the entry starts empty (infinity, count 0).  -BGV_E_ARG for an id that is live
+ * or >= BGV_MAX_SIGPOOL.  Replaces the pool's aggregate creation on the first message of a key
+ * (attestationPool.ts aggregateAttestationInto's counterpart for a new data root).
+ *
+ * bgv_sigpool_drop_range: drops the live entries of ids first_id .. first_id + count - 1 and returns
+ * how many there were (>= 0); a dropped id may be opened again at once.  Replaces the pools' prune()
+ * of old slots.
+ *
+ * bgv_sigpool_get: reads n entries without changing them (ids may repeat).  An id >=
+ * BGV_MAX_SIGPOOL gives -BGV_E_ARG and nothing is written.  Per id:
+ *   not live    out_status -BGV_E_BAD_INDEX,        out_count 0, out96 zero
+ *   count 0     out_status -BGV_E_EMPTY_AGGREGATE,  out_count 0, out96 zero
+ *   otherwise   out_status 0, the entry's count, the compressed sum: byte for byte
+ *               bgv_aggregate_signatures' over the same signatures (the infinity encoding for a sum
+ *               at infinity)
+ * Replaces AttestationPool.getAggregate / SyncCommitteeMessagePool.getContribution's
+ * signature.toBytes().
+ *
+ * bgv_verify_accumulate: bgv_verify_spans whose accepted signatures are added to pool entries.
+ * Replaces verifySignatureSets followed by AttestationPool.add / SyncCommitteeMessagePool.add's
+ * curve arithmetic (network/gossip/handlers/index.ts:199,285).
+ *   out_job_codes    exactly those of bgv_verify_spans on the same arguments (spans may be NULL)
+ *   pool_of_set[i]   the entry set i is added to, or BGV_NO_AGG; NULL: the call is bgv_verify_spans
+ *   out_added[i]     (may be NULL) 1 iff set i was added
+ * All tags are checked at submit: one that is neither BGV_NO_AGG nor < BGV_MAX_SIGPOOL gives
+ * -BGV_E_ARG; otherwise one that names an entry that is not live gives -BGV_E_BAD_INDEX; in both
+ * cases nothing runs and no output is written.  Set i is added iff the code of the job that holds
+ * it is 1, it is tagged, and its entry is still the one that was open at submit: an entry dropped
+ * since, or dropped and opened again, receives nothing from this call.  As in bgv_verify_aggregate a
+ * repeated signature counts again, an infinity signature adds nothing and is counted, and the
+ * signatures are read from sets[i].sig once the codes are final: the caller keeps them alive and
+ * unchanged until the call returns (until done() in the asynchronous form).  If a member no longer
+ * decodes, its entry is left exactly as it was and none of that entry's sets of this call count as
+ * added.  A failed call (negative return) changes no entry.  Every accepted signature is added
+ * exactly once, whatever retry rounds, split calls or merged super-batches the verdicts went through.
+ * Accumulation steps of one context are serialised with each other and with get / drop: after a
+ * synchronous call returns, or an asynchronous call's done() has fired (on a worker thread of the
+ * context), bgv_sigpool_get sees that call's additions.  bgv_close ends a call whose step is still
+ * queued with -BGV_E_CLOSED: the codes stand, the entries are not written.
+ * The decoding form is bgv_verify_aggregate's: at most BGV_SIGAGG_WAVE_MAX added signatures decode
+ * one per wavefront, more one per lane. */
+#define BGV_MAX_SIGPOOL 16384 /* ids 0..16383 */
+int bgv_sigpool_open(bgv_ctx* ctx, uint32_t id);
+int bgv_sigpool_drop_range(bgv_ctx* ctx, uint32_t first_id, uint32_t count);
+int bgv_sigpool_get(bgv_ctx* ctx, const uint32_t* ids, size_t n, uint8_t* out96, uint32_t* out_count,
+                    int32_t* out_status);
+int bgv_verify_accumulate(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                          const bgv_pkspan* spans, int mode, const uint32_t* pool_of_set, int32_t* out_job_codes,
+                          uint8_t* out_added, bgv_stats* stats);
+int bgv_verify_accumulate_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                                const bgv_pkspan* spans, int mode, const uint32_t* pool_of_set,
+                                int32_t* out_job_codes, uint8_t* out_added, bgv_stats* stats, bgv_done_fn done,
+                                void* user);
+
+/* Parity hook (tests only): how many accumulation steps on this context have launched the
+ * one-signature-per-wavefront decoding (out[0]) and the one-per-lane decoding (out[1]); a step that
+ * adds nothing launches neither. */
+int bgv_debug_sigpool_launches(bgv_ctx* ctx, uint64_t out[2]);
+
 /* Deposit signature check (processDeposit.ts:62-70): key validated as above, then
  * Signature.fromBytes(sig, affine, true).verify(pk, signingRoot); any BLS error counts
  * as invalid.  out_valid[i] = 1 or 0. */

@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libblsgpu.so")
 # kernel translation units (compiled in parallel; each carries its own copy of the
 # out-of-line arithmetic with its own register budget) and the host orchestration units
-KERNEL_UNITS = ["bgv_k_prep_bulk.hip", "bgv_k_miller_bulk.hip", "bgv_k_prep.hip", "bgv_k_prep_wave.hip", "bgv_k_miller.hip", "bgv_k_final.hip", "bgv_k_util.hip", "bgv_k_shuffle.hip", "bgv_k_sample.hip", "bgv_k_sigagg.hip"]
-HOST_UNITS = ["bgv_sched.cpp", "bgv_registry.cpp", "bgv_calls.cpp", "bgv_sigagg.cpp"]
+KERNEL_UNITS = ["bgv_k_prep_bulk.hip", "bgv_k_miller_bulk.hip", "bgv_k_prep.hip", "bgv_k_prep_wave.hip", "bgv_k_miller.hip", "bgv_k_final.hip", "bgv_k_util.hip", "bgv_k_shuffle.hip", "bgv_k_sample.hip", "bgv_k_sigagg.hip", "bgv_k_sigpool.hip"]
+HOST_UNITS = ["bgv_sched.cpp", "bgv_registry.cpp", "bgv_calls.cpp", "bgv_sigagg.cpp", "bgv_sigpool.cpp"]
 SOURCES = [os.path.join(CSRC, f) for f in KERNEL_UNITS + HOST_UNITS]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("BGV_OFFLOAD_ARCH", "gfx950")

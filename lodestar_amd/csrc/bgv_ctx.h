@@ -172,6 +172,22 @@ struct SigAggScratch {
   Pinned<uint32_t> h_fc;
 };
 
+// Signature pools (bgv_sigpool.cpp; under util_mu): the accumulators, and the scratch of the
+// accumulation step and of bgv_sigpool_get beside SigAggScratch's signatures, points and statuses,
+// which the step shares.  Grown to the largest call seen.
+struct SigPoolDev {
+  void* d_acc = nullptr;       // BGV_MAX_SIGPOOL x bgv_g2_point_bytes(), allocated at the first open
+  uint32_t* d_meta = nullptr;  // ids[cap], first[cap], count[cap], fresh[cap] of the touched entries
+  int32_t* d_flag = nullptr;   // cap
+  size_t cap = 0;
+  uint32_t* d_gids = nullptr;  // bgv_sigpool_get: get_cap ids and their compressed sums
+  uint8_t* d_gout = nullptr;
+  size_t get_cap = 0;
+  Pinned<uint32_t> h_meta, h_gids;
+  Pinned<int32_t> h_flag;
+  Pinned<uint8_t> h_gout;
+};
+
 // Device-resident committees (bgv_committee_put).  Every device keeps a directory of
 // kComHandles entries (bgv_dcommittee: where the members are, how many, their pubkey sum) and one
 // pool of member indices; a committee has the same handle and pool range on every device.  The
@@ -247,7 +263,31 @@ struct CommitteeRec {
 };
 
 struct Call;
-struct SigAggTask;
+struct bgv_ctx;
+// One bgv_verify_aggregate or bgv_verify_accumulate call between its verdicts and its step on
+// device 0's utility stream (the context's aggregation worker runs the asynchronous ones).
+struct SigAggTask {
+  bgv_ctx* c = nullptr;
+  const bgv_job* jobs = nullptr;
+  size_t njobs = 0;
+  const bgv_set* sets = nullptr;
+  size_t nsets = 0;
+  const uint32_t* agg_of_set = nullptr;  // bgv_verify_accumulate: pool_of_set
+  size_t naggs = 0;
+  const int32_t* codes = nullptr;
+  uint8_t* out96 = nullptr;
+  int32_t* out_status = nullptr;
+  uint32_t* out_count = nullptr;
+  bgv_stats* stats = nullptr;
+  bgv_done_fn done = nullptr;
+  void* user = nullptr;
+  std::chrono::steady_clock::time_point t0;
+  // the step, when it is not the aggregation: bgv_verify_accumulate's, with the generation of every
+  // set's entry at submit and out_added
+  int (*step)(const SigAggTask&) = nullptr;
+  std::vector<uint32_t> gen_of_set;
+  uint8_t* out_added = nullptr;
+};
 // What a super-batch's retry rounds need from its first pass.
 struct BatchState {
   std::chrono::steady_clock::time_point tb;
@@ -296,6 +336,7 @@ struct Device {
   uint32_t* shuf_buf = nullptr;       // bgv_shuffling_put's scratch (active indices, digest table, pivots)
   size_t shuf_cap = 0;                // in words; grown on demand, under util_mu
   SigAggScratch sigagg;               // device 0 only
+  SigPoolDev sigpool;                 // device 0 only
   std::vector<Exec*> execs;
   // held while one super-batch runs its per-set kernels (pointer: Device stays movable)
   std::unique_ptr<std::mutex> compute_mu = std::make_unique<std::mutex>();
@@ -376,6 +417,13 @@ struct bgv_ctx {
   bool agg_stop = false;
   // aggregation steps launched with the wavefront form [0] and the lane form [1] (bgv_debug_sigagg_launches)
   std::atomic<uint64_t> sigagg_launches[2] = {};
+  // Signature pools (bgv_sigpool.cpp): per id whether it is live, its generation (changed by every
+  // open), how many signatures it holds and whether its accumulator has been written since it was
+  // opened.  pool_mu guards these; whoever also works on the device takes util_mu first.
+  std::mutex pool_mu;
+  std::vector<uint8_t> pool_live, pool_written;
+  std::vector<uint32_t> pool_gen, pool_count;
+  std::atomic<uint64_t> sigpool_launches[2] = {};  // as sigagg_launches (bgv_debug_sigpool_launches)
   // dispatch
   std::vector<std::thread> dispatchers;
   std::mutex qmu;
@@ -430,5 +478,11 @@ void fp12_one_bytes(uint8_t out[576]);
 // bgv_sigagg.cpp
 void sigagg_stop(bgv_ctx* c);   // bgv_close: queued aggregations end with -BGV_E_CLOSED, the worker is joined
 void sigagg_free(Device& d);    // ctx_free_devices
+size_t sigagg_wave_max();
+int sigagg_reserve(SigAggScratch& s, size_t n, size_t naggs);
+int sigagg_worker_start(bgv_ctx* c);          // BGV_OK, or -BGV_E_CLOSED once bgv_close has begun
+void sigagg_verify_done(void* user, int rc);  // a verify call's done(): hands its SigAggTask to the worker
+// bgv_sigpool.cpp
+void sigpool_free(Device& d);  // ctx_free_devices
 
 #pragma GCC visibility pop

@@ -83,6 +83,17 @@ __global__ void BGV_KATTR k_sigagg_sum(const uint32_t* __restrict__ first, const
 
 }  // extern "C"
 
+// the decoding alone (bgv_sigpool.cpp: the pool's accumulation step sums the points itself)
+hipError_t bgv_launch_sigagg_decode(const uint8_t* sigs96, uint32_t n, bool wave, void* pts, int32_t* status,
+                                    hipStream_t st) {
+  g2_jac* p = reinterpret_cast<g2_jac*>(pts);
+  if (n && wave)
+    hipLaunchKernelGGL(k_sigagg_decode_wave, dim3(n), dim3(BGV_WAVE), 0, st, sigs96, n, p, status);
+  else if (n)
+    hipLaunchKernelGGL(k_sigagg_decode_lane, dim3(nblk(n, BGV_WAVE)), dim3(BGV_WAVE), 0, st, sigs96, n, p, status);
+  return hipGetLastError();
+}
+
 hipError_t bgv_launch_sigagg(const uint8_t* sigs96, uint32_t n, bool wave, const uint32_t* first,
                              const uint32_t* count, uint32_t naggs, void* pts, int32_t* status, uint8_t* out96,
                              hipStream_t st) {

@@ -175,6 +175,18 @@ size_t bgv_g2_point_bytes();
 hipError_t bgv_launch_sigagg(const uint8_t* sigs96, uint32_t n, bool wave, const uint32_t* first,
                              const uint32_t* count, uint32_t naggs, void* pts, int32_t* status, uint8_t* out96,
                              hipStream_t st);
+// the decoding of bgv_launch_sigagg alone
+hipError_t bgv_launch_sigagg_decode(const uint8_t* sigs96, uint32_t n, bool wave, void* pts, int32_t* status,
+                                    hipStream_t st);
+// Signature pools (bgv_k_sigpool.hip).  acc: BGV_MAX_SIGPOOL g2_jac accumulators.  One wavefront
+// per touched entry e adds pts[first[e] .. first[e] + count[e]) to acc[ids[e]] (taken as infinity
+// when fresh[e]); flag[e] receives 0, or the status of the first member that did not decode, and
+// then the accumulator is not written.
+hipError_t bgv_launch_sigpool_acc(const uint32_t* ids, const uint32_t* first, const uint32_t* count,
+                                  const uint32_t* fresh, uint32_t nentries, const void* pts, const int32_t* status,
+                                  void* acc, int32_t* flag, hipStream_t st);
+// out96[a] = acc[ids[a]], compressed; every named accumulator has been written
+hipError_t bgv_launch_sigpool_get(const uint32_t* ids, uint32_t n, const void* acc, uint8_t* out96, hipStream_t st);
 size_t bgv_fp12_bytes();
 hipError_t bgv_launch_fp12_bytes(const fp12_t* in, uint32_t n, uint8_t* out576, hipStream_t st);  // parity hooks
 hipError_t bgv_launch_partial(const bgv_dev_batch& b, uint32_t g0, uint32_t ng, void* scratch, uint8_t* out576,

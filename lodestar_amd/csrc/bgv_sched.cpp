@@ -872,6 +872,7 @@ static void ctx_free_devices(bgv_ctx* c) {
       d.shuf_buf = nullptr;
       d.shuf_cap = 0;
       sigagg_free(d);
+      sigpool_free(d);
       d.com_dir = nullptr;
       d.com_pool = nullptr;
       d.com_list = nullptr;

@@ -8,7 +8,7 @@
 // accepted signatures up to which a call decodes one per wavefront: the header's value unless
 // BGV_SIGAGG_WAVE_MAX is set in the environment (0: always one per lane).  Not env_size, which
 // reads an unset variable as 0 when 0 is allowed.
-static size_t sigagg_wave_max() {
+size_t sigagg_wave_max() {
   static const size_t v = [] {
     const char* e = getenv("BGV_SIGAGG_WAVE_MAX");
     return e && *e ? (size_t)strtoull(e, nullptr, 10) : (size_t)BGV_SIGAGG_WAVE_MAX;
@@ -16,26 +16,7 @@ static size_t sigagg_wave_max() {
   return v;
 }
 
-// One bgv_verify_aggregate call between its verdicts and its aggregates.
-struct SigAggTask {
-  bgv_ctx* c = nullptr;
-  const bgv_job* jobs = nullptr;
-  size_t njobs = 0;
-  const bgv_set* sets = nullptr;
-  size_t nsets = 0;
-  const uint32_t* agg_of_set = nullptr;
-  size_t naggs = 0;
-  const int32_t* codes = nullptr;
-  uint8_t* out96 = nullptr;
-  int32_t* out_status = nullptr;
-  uint32_t* out_count = nullptr;
-  bgv_stats* stats = nullptr;
-  bgv_done_fn done = nullptr;
-  void* user = nullptr;
-  std::chrono::steady_clock::time_point t0;
-};
-
-static int sigagg_reserve(SigAggScratch& s, size_t n, size_t naggs) {
+int sigagg_reserve(SigAggScratch& s, size_t n, size_t naggs) {
   if (n > s.sig_cap) {
     void* bufs[] = {s.d_sigs, s.d_pts, s.d_st};
     for (void* q : bufs)
@@ -164,13 +145,13 @@ static void sigagg_worker_loop(bgv_ctx* c) {
       stop = c->agg_stop;
     }
     // bgv_close ends queued work: the verdicts stand, the aggregates are not written
-    sigagg_task_end(t, stop ? -BGV_E_CLOSED : sigagg_run(*t));
+    sigagg_task_end(t, stop ? -BGV_E_CLOSED : t->step ? t->step(*t) : sigagg_run(*t));
   }
 }
 
 // The verify call's done(): on a dispatcher or retry thread (or a split call's own thread), which
 // never waits for the device here -- the call goes to the context's aggregation worker.
-static void sigagg_verify_done(void* user, int rc) {
+void sigagg_verify_done(void* user, int rc) {
   SigAggTask* t = static_cast<SigAggTask*>(user);
   bgv_ctx* c = t->c;
   if (rc == BGV_OK) {
@@ -185,6 +166,13 @@ static void sigagg_verify_done(void* user, int rc) {
     return;
   }
   c->agg_cv.notify_one();
+}
+
+int sigagg_worker_start(bgv_ctx* c) {
+  std::lock_guard<std::mutex> lk(c->agg_mu);
+  if (c->agg_stop) return -BGV_E_CLOSED;
+  if (!c->agg_worker.joinable()) c->agg_worker = std::thread(sigagg_worker_loop, c);
+  return BGV_OK;
 }
 
 void sigagg_stop(bgv_ctx* c) {
@@ -244,11 +232,7 @@ int bgv_verify_aggregate_async(bgv_ctx* c, const bgv_job* jobs, size_t njobs, co
   if (int rc = sigagg_check_args(c, nsets, agg_of_set, naggs, out_agg96, out_agg_status, out_agg_count)) return rc;
   if (naggs == 0) return bgv_verify_spans_async(c, jobs, njobs, sets, nsets, spans, mode, out, stats, done, user);
   if (!done) return -BGV_E_ARG;  // nobody to tell of the aggregates
-  {
-    std::lock_guard<std::mutex> lk(c->agg_mu);
-    if (c->agg_stop) return -BGV_E_CLOSED;
-    if (!c->agg_worker.joinable()) c->agg_worker = std::thread(sigagg_worker_loop, c);
-  }
+  if (int rc = sigagg_worker_start(c)) return rc;
   SigAggTask* t = new SigAggTask();
   t->t0 = std::chrono::steady_clock::now();
   t->c = c;

@@ -40,6 +40,7 @@ NO_PROPOSER = 0xFFFFFFFF
 SAMPLE_MAX_TRIES = 65536
 NO_AGG = 0xFFFFFFFF
 SIGAGG_WAVE_MAX = 2048  # BGV_SIGAGG_WAVE_MAX of include/blsgpu.h
+MAX_SIGPOOL = 16384  # BGV_MAX_SIGPOOL
 
 EXPORTED_SYMBOLS = [
     "bgv_init", "bgv_close", "bgv_destroy", "bgv_pubkeys_put", "bgv_pubkeys_count", "bgv_verify",
@@ -52,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "bgv_proposers", "bgv_sync_committee_put", "bgv_proposers_electra", "bgv_sync_committee_put_electra",
     "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
     "bgv_verify_aggregate", "bgv_verify_aggregate_async", "bgv_debug_sigagg_launches",
+    "bgv_sigpool_open", "bgv_sigpool_drop_range", "bgv_sigpool_get", "bgv_verify_accumulate",
+    "bgv_verify_accumulate_async", "bgv_debug_sigpool_launches",
 ]
 
 
@@ -152,6 +155,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_debug_sigagg_launches": ([P, P], ctypes.c_int),
             "bgv_verify_aggregate_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, SZ, P, P, P, P, P, DONE_FN, P],
                                            ctypes.c_int),
+            "bgv_sigpool_open": ([P, U32], ctypes.c_int),
+            "bgv_sigpool_drop_range": ([P, U32, U32], ctypes.c_int),
+            "bgv_sigpool_get": ([P, P, SZ, P, P, P], ctypes.c_int),
+            "bgv_verify_accumulate": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P], ctypes.c_int),
+            "bgv_verify_accumulate_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P, DONE_FN, P], ctypes.c_int),
+            "bgv_debug_sigpool_launches": ([P, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
@@ -161,7 +170,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                         "bgv_proposers_electra", "bgv_sync_committee_put_electra",
                         "bgv_verify_spans", "bgv_verify_spans_async", "bgv_aggregate_span",
                         "bgv_verify_aggregate", "bgv_verify_aggregate_async",
-                        "bgv_debug_sigagg_launches") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_debug_sigagg_launches", "bgv_sigpool_open", "bgv_sigpool_drop_range",
+                        "bgv_sigpool_get", "bgv_verify_accumulate", "bgv_verify_accumulate_async",
+                        "bgv_debug_sigpool_launches") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -550,6 +561,57 @@ class Context:
             raise ValueError("agg_of_set takes one entry per set")
         return PendingAggregate(self, packed, agg_of_set, naggs, mode)
 
+    # --- device-resident signature pools (bgv_sigpool_open) --------------------
+    def sigpool_open(self, pool_id: int):
+        """Open pool entry pool_id (0 .. MAX_SIGPOOL - 1): a G2 accumulator, empty, with a count."""
+        _check(self.lib.bgv_sigpool_open(self._h, pool_id))
+
+    def sigpool_drop_range(self, first_id: int, count: int) -> int:
+        """Drop the live entries of ids first_id .. first_id + count - 1; returns how many."""
+        return _check(self.lib.bgv_sigpool_drop_range(self._h, first_id, count))
+
+    def sigpool_get(self, ids: Sequence[int]):
+        """bgv_sigpool_get: [(status, count, compressed96)] per id, entries unchanged."""
+        n = len(ids)
+        arr = (ctypes.c_uint32 * max(1, n))(*ids)
+        out = ctypes.create_string_buffer(96 * max(1, n))
+        cnt = (ctypes.c_uint32 * max(1, n))()
+        st = (ctypes.c_int32 * max(1, n))()
+        _check(self.lib.bgv_sigpool_get(self._h, arr, n, out, cnt, st))
+        return [(st[k], cnt[k], out.raw[96 * k:96 * k + 96]) for k in range(n)]
+
+    def verify_accumulate(self, jobs, pool_of_set: Sequence[int], mode: int = MODE_WORKER,
+                          stats: Optional[BgvStats] = None):
+        """bgv_verify_accumulate: verify_jobs whose accepted signatures are added to pool entries.
+        pool_of_set[i] is the entry of set i (in job order) or NO_AGG.  Returns (codes, added) with
+        added[i] True iff set i was added."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(pool_of_set) != packed.nsets:
+            raise ValueError("pool_of_set takes one entry per set")
+        njobs = len(packed.jobs_in)
+        out = (ctypes.c_int32 * max(1, njobs))()
+        tags = (ctypes.c_uint32 * max(1, packed.nsets))(*pool_of_set)
+        added = (ctypes.c_uint8 * max(1, packed.nsets))()
+        st = ctypes.byref(stats) if stats is not None else None
+        _check(self.lib.bgv_verify_accumulate(self._h, packed.jobs, njobs, packed.sets, packed.nsets,
+                                              packed.as_spans(), mode, tags, out, added, st))
+        return list(out[:njobs]), [bool(a) for a in added[:packed.nsets]]
+
+    def verify_accumulate_async(self, jobs, pool_of_set: Sequence[int], mode: int = MODE_WORKER):
+        """bgv_verify_accumulate_async: returns a PendingAccumulate whose wait() gives what
+        verify_accumulate returns; the additions are visible to sigpool_get once it has returned."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(pool_of_set) != packed.nsets:
+            raise ValueError("pool_of_set takes one entry per set")
+        return PendingAccumulate(self, packed, pool_of_set, mode)
+
+    def sigpool_launches(self):
+        """bgv_debug_sigpool_launches (parity hook): accumulation steps launched so far with the
+        (wavefront, lane) decoding form."""
+        out = (ctypes.c_uint64 * 2)()
+        _check(self.lib.bgv_debug_sigpool_launches(self._h, out))
+        return out[0], out[1]
+
 
 class PendingVerify:
     """One bgv_verify_async / bgv_verify_bits_async / bgv_verify_spans_async call: keeps its
@@ -622,6 +684,38 @@ class PendingAggregate:
     def wait(self, timeout: Optional[float] = None):
         if not self._event.wait(timeout):
             raise TimeoutError("bgv_verify_aggregate_async: done() has not fired")
+        _check(self._rc)
+        return self._result
+
+
+class PendingAccumulate:
+    """One bgv_verify_accumulate_async call: keeps its buffers alive until done() has fired on the
+    context's worker thread, where the outputs are read."""
+
+    def __init__(self, ctx: "Context", packed: "PackedCall", pool_of_set: Sequence[int], mode: int):
+        self._packed = packed
+        njobs, nsets = len(packed.jobs_in), packed.nsets
+        self._out = (ctypes.c_int32 * max(1, njobs))()
+        self._tags = (ctypes.c_uint32 * max(1, nsets))(*pool_of_set)
+        self._added = (ctypes.c_uint8 * max(1, nsets))()
+        self.stats = BgvStats()
+        self._event = threading.Event()
+        self._rc = None
+        self._result = None
+
+        def done(_user, rc):
+            self._rc = rc
+            self._result = (list(self._out[:njobs]), [bool(a) for a in self._added[:nsets]])
+            self._event.set()
+
+        self._done = DONE_FN(done)
+        _check(ctx.lib.bgv_verify_accumulate_async(ctx.handle, packed.jobs, njobs, packed.sets, nsets,
+                                                   packed.as_spans(), mode, self._tags, self._out, self._added,
+                                                   ctypes.byref(self.stats), self._done, None))
+
+    def wait(self, timeout: Optional[float] = None):
+        if not self._event.wait(timeout):
+            raise TimeoutError("bgv_verify_accumulate_async: done() has not fired")
         _check(self._rc)
         return self._result
 

@@ -317,14 +317,50 @@ class BlsGpuVerifier {
     return this._sameMessage(sets, message, opts, true);
   }
 
-  async _sameMessage(sets, message, opts, aggregate) {
+  /**
+   * verifySignatureSetsSameMessage whose device call also adds the signatures it accepted to the
+   * device-resident pool entry poolId (bgv_verify_accumulate; poolOpen, poolGet): resolves to one
+   * boolean per set, true iff the set was accepted and added.  The op pool's running aggregate
+   * (opPools/attestationPool.ts:184-187, syncCommitteeMessagePool.ts:126-129) then needs no curve
+   * arithmetic on the host: the node reads 96 bytes once, when an aggregator asks (poolGet).
+   */
+  async verifyAndPoolSameMessage(sets, message, poolId, opts = {}) {
+    return (await this._sameMessage(sets, message, opts, false, poolId)).results;
+  }
+
+  async _sameMessage(sets, message, opts, aggregate, pool) {
     if (this.pendingRuns.length || this.flushing) await this.flushPubkeys();
     if (sets.length === 0) return {results: [], signature: null};
     const native = sets.map((s) =>
       toNativeSet({type: SignatureSetType.single, pubkey: s.publicKey, signingRoot: message, signature: s.signature})
     );
     // one unit in the buffer and one device call, whatever its size; each set its own job there
-    return this.queueBlsWork({opts: {...opts, batchable: true}, sets: native, perSet: true, aggregate});
+    return this.queueBlsWork({opts: {...opts, batchable: true}, sets: native, perSet: true, aggregate, pool});
+  }
+
+  /** Opens the device-resident signature pool entry `id` (0..16383), empty (INTEGRATION.md §2e). */
+  poolOpen(id) {
+    addon.sigpoolOpen(this.ctx, id);
+  }
+
+  /** Drops the live entries of ids first .. first + count - 1 (a pruned slot's); returns how many. */
+  poolDropRange(first, count) {
+    return addon.sigpoolDropRange(this.ctx, first, count);
+  }
+
+  /**
+   * Reads entries without changing them, off the event loop: per id {status, count, signature},
+   * status 0 with the compressed aggregate of the `count` signatures added so far, else a negative
+   * library code (not open, or nothing added yet) with signature null.
+   */
+  async poolGet(ids) {
+    const arr = ids instanceof Uint32Array ? ids : Uint32Array.from(ids);
+    const {status, count, sigs} = await addon.sigpoolGet(this.ctx, arr);
+    return Array.from(arr, (_, k) => ({
+      status: status[k],
+      count: count[k],
+      signature: status[k] === 0 ? sigs.slice(96 * k, 96 * k + 96) : null,
+    }));
   }
 
   /** IBlsVerifier.canAcceptWork: false while the sets queued or in flight reach opts.maxInflightSigs. */
@@ -428,10 +464,17 @@ class BlsGpuVerifier {
       const job = {resolve, reject, workReq, addedTimeMs: Date.now()};
       this.inflightSigs += workReq.sets.length;
       if (workReq.opts.batchable) {
+        // a buffered run holds one kind of caller: a pool caller does not join aggregate callers, nor the reverse
+        const kind = callerKind(workReq);
+        if (this.bufferedJobs && kind && this.bufferedJobs.kind && this.bufferedJobs.kind !== kind) {
+          clearTimeout(this.bufferedJobs.timeout);
+          this.runBufferedJobs();
+        }
         if (!this.bufferedJobs) {
           this.bufferedJobs = {jobs: [], sigCount: 0, timeout: setTimeout(this.runBufferedJobs, this.maxBufferWaitMs)};
         }
         this.bufferedJobs.jobs.push(job);
+        this.bufferedJobs.kind = this.bufferedJobs.kind || kind;
         this.bufferedJobs.sigCount += workReq.sets.length;
         if (this.bufferedJobs.sigCount > this.maxBufferedSigs) {
           clearTimeout(this.bufferedJobs.timeout);
@@ -455,11 +498,27 @@ class BlsGpuVerifier {
   // Scheduled with setImmediate where index.ts uses setTimeout(runJob, 0): jobs queued in the
   // same macrotask still leave in one call, without Node's 1 ms floor on a zero timeout (a
   // whole millisecond on every gossip batch's critical path).
-  // All queued jobs go to the device in one call; the library merges concurrent calls into
-  // super-batches, so there is no idle-worker bookkeeping here (index.ts:290-381).
+  // All queued jobs go to the device in one call -- one per kind of caller where runs of both
+  // kinds were flushed together; the library merges concurrent calls into super-batches, so there
+  // is no idle-worker bookkeeping here (index.ts:290-381).
   runJob = async () => {
     if (this.closed || this.jobs.length === 0) return;
-    const jobs = this.jobs.splice(0, this.jobs.length);
+    const all = this.jobs.splice(0, this.jobs.length);
+    const calls = [[]];
+    let kind = null;
+    for (const job of all) {
+      const k = callerKind(job.workReq);
+      if (k && kind && k !== kind) {
+        calls.push([]);
+        kind = null;
+      }
+      kind = kind || k;
+      calls[calls.length - 1].push(job);
+    }
+    await Promise.all(calls.map((jobs) => this.runCall(jobs)));
+  };
+
+  runCall = async (jobs) => {
     const m = this.metrics ? this.metrics.blsThreadPool : null;
     let startedSigSets = 0;
     for (const job of jobs) {
@@ -472,23 +531,34 @@ class BlsGpuVerifier {
       m.totalSigSetsStarted.inc(startedSigSets);
     }
     // A same-message caller's sets travel as one-set jobs from `first` on; with an aggregate
-    // wanted they carry an id of their own within this call.  Without a tagged set the call is
-    // addon.verify, exactly as before.
+    // wanted they carry an id of their own within this call, with a pool entry named that entry.
+    // Without a tagged set the call is addon.verify, exactly as before.
     const nativeJobs = [];
     let naggs = 0;
+    let pooled = false;
+    let nsets = 0;
     for (const job of jobs) {
       const w = job.workReq;
       job.first = nativeJobs.length;
+      job.firstSet = nsets;
+      nsets += w.sets.length;
       if (!w.perSet) {
         nativeJobs.push({sets: w.sets, batchable: Boolean(w.opts.batchable)});
         continue;
       }
       job.agg = w.aggregate ? naggs++ : -1;
-      for (const s of w.sets) nativeJobs.push({sets: [job.agg < 0 ? s : {...s, agg: job.agg}], batchable: true});
+      const tag = w.pool !== undefined ? {pool: w.pool} : job.agg >= 0 ? {agg: job.agg} : null;
+      pooled = pooled || w.pool !== undefined;
+      for (const s of w.sets) nativeJobs.push({sets: [tag ? {...s, ...tag} : s], batchable: true});
     }
     try {
-      let codes, aggs;
-      if (naggs) {
+      let codes, aggs, added;
+      if (pooled) {
+        const res = await addon.verifyAccumulate(this.ctx, nativeJobs, 0);
+        codes = res.codes;
+        codes.stats = res.stats;
+        added = res.added;
+      } else if (naggs) {
         const res = await addon.verifyAggregate(this.ctx, nativeJobs, 0);
         codes = res.codes;
         codes.stats = res.stats;
@@ -502,7 +572,8 @@ class BlsGpuVerifier {
         const w = job.workReq;
         if (w.perSet) {
           // per set: an error code is false for that set (the interface's per-set retry), never a rejection
-          const results = w.sets.map((_, k) => codes[job.first + k] === 1);
+          const inPool = w.pool !== undefined;
+          const results = w.sets.map((_, k) => codes[job.first + k] === 1 && (!inPool || added[job.firstSet + k] === 1));
           w.sets.forEach((_, k) => (codes[job.first + k] < 0 ? errorCount++ : successCount++));
           const ok = job.agg >= 0 && aggs.status[job.agg] === 0;
           job.resolve({results, signature: ok ? aggs.sigs.slice(96 * job.agg, 96 * job.agg + 96) : null});
@@ -593,6 +664,11 @@ class BlsGpuVerifier {
     });
     return Array.from(addon.depositsVerify(this.ctx, keys, roots, sigs), (v) => v === 1);
   }
+}
+
+// which kind of same-message caller a unit of work is: "pool", "aggregate" or null
+function callerKind(w) {
+  return w.pool !== undefined ? "pool" : w.aggregate ? "aggregate" : null;
 }
 
 function unwrap(code) {

@@ -21,6 +21,10 @@
  *   verify(ctx, jobs: {sets: {pkIndices: Uint32Array | pkBytes: Uint8Array (n x 96),
  *                             msg: Uint8Array, sig: Uint8Array}[], batchable: boolean}[],
  *          mode: 0 | 1) -> Promise<Int32Array>   (1 valid, 0 invalid, -code error)
+ *   verifyAccumulate(ctx, jobs (sets may carry pool: number), mode)
+ *          -> Promise<{codes, stats, added: Uint8Array}>   (bgv_verify_accumulate_async)
+ *   sigpoolOpen(ctx, id), sigpoolDropRange(ctx, firstId, count) -> number
+ *   sigpoolGet(ctx, ids: Uint32Array) -> Promise<{status, count, sigs}>  (on a libuv pool thread)
  *   strerror(code) -> string
  *   close(ctx)
  * SURVEY 8(f) entry points and parity hooks (synchronous):
@@ -120,8 +124,10 @@ typedef struct {
   napi_deferred deferred;
   napi_ref* refs; /* keep every input buffer alive until completion */
   size_t nrefs;
-  /* verifyAggregate: the sets' `agg` tags beside sets, and the aggregates' outputs */
+  /* verifyAggregate (1): the sets' `agg` tags beside sets, and the aggregates' outputs;
+   * verifyAccumulate (2): the sets' `pool` tags in tags, and per set whether it was added */
   int aggregate;
+  uint8_t* added;
   uint32_t* tags;
   size_t naggs;
   uint8_t* agg96;
@@ -409,6 +415,123 @@ static napi_value js_committee_drop_range(napi_env env, napi_callback_info info)
   if (rc < 0) return throw_code(env, rc);
   CHECK(env, napi_create_int32(env, rc, &out));
   return out;
+}
+
+/* sigpoolOpen(ctx, id): a device-resident signature pool entry, empty (bgv_sigpool_open; host work
+ * after the first call, which allocates the accumulators).
+ * sigpoolDropRange(ctx, firstId, count) -> number: bgv_sigpool_drop_range, the live ids dropped. */
+static napi_value js_sigpool_open(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t id = 0;
+  if (argc < 2 || napi_get_value_uint32(env, argv[1], &id) != napi_ok) return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_sigpool_open(ctx, id);
+  if (rc) return throw_code(env, rc);
+  return NULL;
+}
+
+static napi_value js_sigpool_drop_range(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], out;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t first = 0, count = 0;
+  if (argc < 3 || napi_get_value_uint32(env, argv[1], &first) != napi_ok ||
+      napi_get_value_uint32(env, argv[2], &count) != napi_ok)
+    return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_sigpool_drop_range(ctx, first, count);
+  if (rc < 0) return throw_code(env, rc);
+  CHECK(env, napi_create_int32(env, rc, &out));
+  return out;
+}
+
+/* sigpoolGet(ctx, ids: Uint32Array) -> Promise<{status: Int32Array, count: Uint32Array, sigs:
+ * Uint8Array (n x 96 compressed)}>: bgv_sigpool_get on a libuv pool thread (it waits for the
+ * device); rejects with an Error whose .bgvCode is the negative library code. */
+typedef struct {
+  napi_async_work work;
+  napi_deferred deferred;
+  napi_ref ctx_ref;
+  bgv_ctx* c;
+  uint32_t* ids;
+  size_t n;
+  uint8_t* out96;
+  uint32_t* count;
+  int32_t* status;
+  int rc;
+} pool_get_req;
+
+static void pool_get_execute(napi_env env, void* data) {
+  (void)env;
+  pool_get_req* r = (pool_get_req*)data;
+  r->rc = bgv_sigpool_get(r->c, r->ids, r->n, r->out96, r->count, r->status);
+}
+
+static void pool_get_complete(napi_env env, napi_status status, void* data) {
+  pool_get_req* r = (pool_get_req*)data;
+  if (status == napi_ok && r->rc == 0) {
+    napi_value out, st = new_int32s(env, r->status, r->n), cab, carr, sigs;
+    void* dst;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "status", st);
+    napi_create_arraybuffer(env, 4 * r->n, &dst, &cab);
+    if (r->n) memcpy(dst, r->count, 4 * r->n);
+    napi_create_typedarray(env, napi_uint32_array, r->n, cab, 0, &carr);
+    napi_set_named_property(env, out, "count", carr);
+    sigs = new_bytes(env, 96 * r->n, &dst);
+    if (r->n) memcpy(dst, r->out96, 96 * r->n);
+    napi_set_named_property(env, out, "sigs", sigs);
+    napi_resolve_deferred(env, r->deferred, out);
+  } else {
+    const int rc = status == napi_ok ? r->rc : -BGV_E_ARG;
+    napi_value msg, err, code;
+    napi_create_string_utf8(env, bgv_strerror(rc), NAPI_AUTO_LENGTH, &msg);
+    napi_create_error(env, NULL, msg, &err);
+    napi_create_int32(env, rc, &code);
+    napi_set_named_property(env, err, "bgvCode", code);
+    napi_reject_deferred(env, r->deferred, err);
+  }
+  napi_delete_reference(env, r->ctx_ref);
+  napi_delete_async_work(env, r->work);
+  free(r->ids);
+  free(r->out96);
+  free(r->count);
+  free(r->status);
+  free(r);
+}
+
+static napi_value js_sigpool_get(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2], promise, name;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint8_t* ids;
+  size_t len;
+  napi_typedarray_type tt = napi_uint8_array;
+  bool is_ta = false;
+  if (argc < 2) return throw_code(env, -BGV_E_ARG);
+  napi_is_typedarray(env, argv[1], &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, argv[1], &tt, NULL, NULL, NULL, NULL);
+  if (!is_ta || tt != napi_uint32_array || get_bytes(env, argv[1], &ids, &len)) return throw_code(env, -BGV_E_ARG);
+  pool_get_req* r = (pool_get_req*)calloc(1, sizeof(pool_get_req));
+  r->c = ctx;
+  r->n = len / 4;
+  r->ids = (uint32_t*)calloc(r->n ? r->n : 1, sizeof(uint32_t)); /* a copy: the caller may reuse its array */
+  if (r->n) memcpy(r->ids, ids, 4 * r->n);
+  r->out96 = (uint8_t*)calloc(r->n ? r->n : 1, 96);
+  r->count = (uint32_t*)calloc(r->n ? r->n : 1, sizeof(uint32_t));
+  r->status = (int32_t*)calloc(r->n ? r->n : 1, sizeof(int32_t));
+  if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
+      napi_create_reference(env, argv[0], 1, &r->ctx_ref) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu.sigpoolGet", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, pool_get_execute, pool_get_complete, r, &r->work) != napi_ok ||
+      napi_queue_async_work(env, r->work) != napi_ok) {
+    napi_throw_error(env, NULL, "blsgpu: N-API failure");
+    return NULL;
+  }
+  return promise;
 }
 
 /* shufflingPut(ctx, firstId, seed: Uint8Array(32), activeIndices: Uint32Array, slots,
@@ -801,6 +924,7 @@ static void free_req_heap(verify_req* r) {
   free(r->agg96);
   free(r->agg_status);
   free(r->agg_count);
+  free(r->added);
   free(r);
 }
 
@@ -843,11 +967,18 @@ static void settle(napi_env env, verify_req* r) {
     napi_resolve_deferred(env, r->deferred, arr);
     return;
   }
-  /* verifyAggregate: {codes, stats, aggs: {status, count, sigs}} */
+  /* verifyAggregate: {codes, stats, aggs: {status, count, sigs}}; verifyAccumulate: {codes, stats, added} */
   napi_value res, aggs, sab, sarr, cab, carr, sigs;
   napi_create_object(env, &res);
   napi_set_named_property(env, res, "codes", arr);
   napi_set_named_property(env, res, "stats", st);
+  if (r->aggregate == 2) {
+    napi_value added = new_bytes(env, r->nsets, &dst);
+    if (r->nsets) memcpy(dst, r->added, r->nsets);
+    napi_set_named_property(env, res, "added", added);
+    napi_resolve_deferred(env, r->deferred, res);
+    return;
+  }
   napi_create_object(env, &aggs);
   napi_create_arraybuffer(env, 4 * r->naggs, &dst, &sab);
   memcpy(dst, r->agg_status, 4 * r->naggs);
@@ -917,7 +1048,9 @@ static void addon_finalize(napi_env env, void* data, void* hint) {
 /* verify(ctx, jobs, mode) resolves to the codes (an Int32Array with .stats); verifyAggregate(ctx,
  * jobs, mode), whose sets may carry `agg: number` (the aggregate the set's signature joins when its
  * job is accepted; bgv_verify_aggregate), to {codes, stats, aggs: {status, count, sigs}} with one
- * entry per aggregate 0 .. the largest agg given */
+ * entry per aggregate 0 .. the largest agg given; verifyAccumulate(ctx, jobs, mode), whose sets may
+ * carry `pool: number` (the open signature pool entry the set's signature is added to when its job
+ * is accepted; bgv_verify_accumulate), to {codes, stats, added: Uint8Array (1 per set that was added)} */
 static napi_value verify_start(napi_env env, napi_callback_info info, int aggregate) {
   size_t argc = 3;
   napi_value argv[3];
@@ -995,12 +1128,12 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
       memset(&r->spans[r->nsets], 0, sizeof(bgv_pkspan));
       r->tags[r->nsets] = BGV_NO_AGG;
       bool tagged = false;
-      if (aggregate) napi_has_named_property(env, s, "agg", &tagged);
+      if (aggregate) napi_has_named_property(env, s, aggregate == 2 ? "pool" : "agg", &tagged);
       if (tagged) {
         napi_value av;
         uint32_t tag = 0;
-        napi_get_named_property(env, s, "agg", &av);
-        if (napi_get_value_uint32(env, av, &tag) != napi_ok || tag >= (1u << 20)) {
+        napi_get_named_property(env, s, aggregate == 2 ? "pool" : "agg", &av);
+        if (napi_get_value_uint32(env, av, &tag) != napi_ok || tag >= (aggregate == 2 ? BGV_MAX_SIGPOOL : (1u << 20))) {
           free_req(env, r);
           return throw_code(env, -BGV_E_ARG);
         }
@@ -1074,7 +1207,9 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
   CHECK(env, napi_create_reference(env, argv[0], 1, &r->ctx_ref));
   if (a->inflight++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
   int rc;
-  if (aggregate) {
+  if (aggregate == 2) {
+    r->added = (uint8_t*)calloc(r->nsets ? r->nsets : 1, 1);
+  } else if (aggregate) {
     r->agg96 = (uint8_t*)calloc(r->naggs ? r->naggs : 1, 96);
     r->agg_status = (int32_t*)calloc(r->naggs ? r->naggs : 1, sizeof(int32_t));
     r->agg_count = (uint32_t*)calloc(r->naggs ? r->naggs : 1, sizeof(uint32_t));
@@ -1089,7 +1224,10 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
       }
     r->any_span = 1;
   }
-  if (aggregate) {
+  if (aggregate == 2) {
+    rc = bgv_verify_accumulate_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_span ? r->spans : NULL, r->mode,
+                                     r->tags, r->codes, r->added, &r->stats, verify_done, r);
+  } else if (aggregate) {
     rc = bgv_verify_aggregate_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_span ? r->spans : NULL, r->mode,
                                     r->tags, r->naggs, r->codes, r->agg96, r->agg_status, r->agg_count, &r->stats,
                                     verify_done, r);
@@ -1111,6 +1249,7 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
 
 static napi_value js_verify(napi_env env, napi_callback_info info) { return verify_start(env, info, 0); }
 static napi_value js_verify_aggregate(napi_env env, napi_callback_info info) { return verify_start(env, info, 1); }
+static napi_value js_verify_accumulate(napi_env env, napi_callback_info info) { return verify_start(env, info, 2); }
 
 #define METHOD_ATTR ((napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable))
 
@@ -1125,6 +1264,10 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"sign", NULL, js_sign, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"verify", NULL, js_verify, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"verifyAggregate", NULL, js_verify_aggregate, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"verifyAccumulate", NULL, js_verify_accumulate, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolOpen", NULL, js_sigpool_open, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolDropRange", NULL, js_sigpool_drop_range, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolGet", NULL, js_sigpool_get, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregatePubkeys", NULL, js_aggregate_pubkeys, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeePut", NULL, js_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},

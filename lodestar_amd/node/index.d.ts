@@ -126,6 +126,26 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     message: Uint8Array,
     opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
   ): Promise<{results: boolean[]; signature: Uint8Array | null}>;
+  /**
+   * verifySignatureSetsSameMessage whose device call also adds the accepted sets' signatures to the
+   * device-resident pool entry poolId (poolOpen): true iff the set was accepted and added.  The op
+   * pool's running aggregate then needs no curve arithmetic on the host
+   */
+  verifyAndPoolSameMessage(
+    sets: SameMessageSet[],
+    message: Uint8Array,
+    poolId: number,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<boolean[]>;
+  /** opens the device-resident signature pool entry id (0..16383), empty */
+  poolOpen(id: number): void;
+  /** drops the live entries of ids first .. first + count - 1; returns how many there were */
+  poolDropRange(first: number, count: number): number;
+  /**
+   * reads entries without changing them: status 0 with the compressed aggregate of the `count`
+   * signatures added so far, else a negative library code (not open, nothing added yet) and null
+   */
+  poolGet(ids: Uint32Array | number[]): Promise<{status: number; count: number; signature: Uint8Array | null}[]>;
   canAcceptWork(): boolean;
   close(): Promise<void>;
   /** state-transition pubkey-added hook: (index, 48-byte pubkey, PublicKey?) */

@@ -192,6 +192,30 @@ class BlsGpuVerifier:
         accepted).  opts and buffering as verify_signature_sets_same_message."""
         return await self._same_message(sets, message, True)
 
+    async def verify_and_pool_same_message(self, sets: Sequence[tuple], message: bytes, pool_id: int,
+                                           opts: Optional[VerifySignatureOpts] = None) -> List[bool]:
+        """verify_signature_sets_same_message whose device call also adds the signatures it
+        accepted to the device-resident pool entry pool_id (bgv_verify_accumulate; the entry was
+        opened with Context.sigpool_open and is read with Context.sigpool_get).  One bool per set:
+        True iff the set was accepted and added.  opts and buffering as
+        verify_signature_sets_same_message."""
+        if self.closed:
+            raise QueueError("QUEUE_ABORTED")
+        if len(sets) == 0:
+            return []
+        jobs = [([to_set_spec(ISignatureSet(SignatureSetType.single, signing_root=message, signature=sig,
+                                            pubkey=pk))], True) for pk, sig in sets]
+        stats = native.BgvStats()
+
+        def call():
+            return self.ctx.verify_accumulate(jobs, [pool_id] * len(jobs), native.MODE_WORKER, stats)
+
+        codes, added = await asyncio.get_running_loop().run_in_executor(None, call)
+        self._account(stats)
+        self.metrics["error_sets"] += sum(1 for c in codes if c < 0)
+        self.metrics["success_sets"] += sum(1 for c in codes if c >= 0)
+        return [c == 1 and a for c, a in zip(codes, added)]
+
     async def _same_message(self, sets, message: bytes, aggregate: bool):
         if self.closed:
             raise QueueError("QUEUE_ABORTED")
