@@ -474,7 +474,9 @@ int bgv_debug_sigagg_launches(bgv_ctx* ctx, uint64_t out[2]);
  *   out_added[i]     (may be NULL) 1 iff set i was added
  * All tags are checked at submit: one that is neither BGV_NO_AGG nor < BGV_MAX_SIGPOOL gives
  * -BGV_E_ARG; otherwise one that names an entry that is not live gives -BGV_E_BAD_INDEX; in both
- * cases nothing runs and no output is written.  Set i is added iff the code of the job that holds
+ * cases nothing runs and no output is written.  A tag on an entry that has bits
+ * (bgv_sigpool_open_bits) gives -BGV_E_ARG in the same way: such an entry is fed by
+ * bgv_verify_accumulate_bits alone.  Set i is added iff the code of the job that holds
  * it is 1, it is tagged, and its entry is still the one that was open at submit: an entry dropped
  * since, or dropped and opened again, receives nothing from this call.  As in bgv_verify_aggregate a
  * repeated signature counts again, an infinity signature adds nothing and is counted, and the
@@ -506,6 +508,97 @@ int bgv_verify_accumulate_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs,
  * one-signature-per-wavefront decoding (out[0]) and the one-per-lane decoding (out[1]); a step that
  * adds nothing launches neither. */
 int bgv_debug_sigpool_launches(bgv_ctx* ctx, uint64_t out[2]);
+
+/* Pool entries with participation bits: the aggregate's bitfield beside its signature, so an entry
+ * refuses a member it already holds and bits and signature change in one step.  Replaces the bit
+ * handling of aggregateAttestationInto (chain/opPools/attestationPool.ts:171-189: AlreadyKnown when
+ * the bit is set) and of MatchingDataAttestationGroup.add (aggregatedAttestationPool.ts:231-275,
+ * 315-322: AlreadyKnown for a subset, aggregateInto only for disjoint bitfields), which the host
+ * cannot do at submit: two calls in flight may carry the same attester, and only the accumulation
+ * step sees final codes one call at a time.
+ *
+ * bgv_sigpool_open_bits: bgv_sigpool_open for an entry that also holds a field of n_bits positions
+ * (1 .. BGV_SIGPOOL_MAX_BITS), all clear; another n_bits gives -BGV_E_ARG.  The field lives in the
+ * host registry (the plan needs it before anything is decoded); bgv_sigpool_drop_range and a reopen
+ * clear it, and a reopen may choose another n_bits or none (bgv_sigpool_open).
+ *
+ * bgv_verify_accumulate_bits: bgv_verify_accumulate with bits_of_set[i], the positions set i stands
+ * for in its entry: bits == NULL names the single position `bit`, otherwise bits is a field of
+ * ceil(n_bits / 8) bytes in SSZ bit order (position k is bit k % 8 of byte k / 8).  The tag checks of
+ * bgv_verify_accumulate run first and are unchanged.  Then, for every tagged set whose entry has
+ * bits, -BGV_E_ARG when bits_of_set is NULL, n_bits is not the entry's, the single position is not
+ * below n_bits, or the field has a bit at or past n_bits or no bit at all; nothing runs and nothing
+ * is written.  bits_of_set[i] of an untagged set or of a plain entry's set is ignored, and such a
+ * set behaves exactly as under bgv_verify_accumulate.  The fields are copied at submit: the caller
+ * need not keep them.  (bgv_verify_accumulate itself gives -BGV_E_ARG at submit for a tag on an
+ * entry that has bits.)
+ *   out_job_codes   exactly those of bgv_verify_spans
+ *   out_outcome[i]  (may be NULL) BGV_POOL_*
+ * The step takes an entry's members in set order.  With B the entry's field as the step finds it
+ * plus what earlier sets of this call added, and M the member's: M & B == 0 adds the signature,
+ * B |= M, BGV_POOL_ADDED; otherwise M within B is BGV_POOL_KNOWN (InsertOutcome.AlreadyKnown) and
+ * anything else BGV_POOL_OVERLAP (the reference's NotBetterThan / no aggregateInto); neither touches
+ * the entry.  BGV_POOL_NOT_ADDED: an untagged set, a set of a job whose code is not 1, a set whose
+ * entry changed generation since submit.  A set of a plain entry gets BGV_POOL_ADDED or
+ * BGV_POOL_NOT_ADDED as out_added would.  Only members to be added are uploaded and decoded (the
+ * decoding form follows their number), and a step with nothing to add does no device work.  Field and
+ * count are committed after the device's flags are back: an entry with a member that no longer
+ * decodes keeps its field, count and accumulator, and all of its sets of this call report
+ * BGV_POOL_NOT_ADDED.  Everything else is as stated for bgv_verify_accumulate: every accepted
+ * signature is added at most once, steps are serialised with get / drop / sum, bgv_close ends a
+ * queued step with -BGV_E_CLOSED, done() fires on a worker thread of the context.
+ *
+ * bgv_sigpool_get_bits: bgv_sigpool_get plus, per id, the entry's field in out_bits (n x
+ * BGV_SIGPOOL_BITS_BYTES, zero padded) and its n_bits in out_nbits (0 for a plain or not-live
+ * entry).  An empty live entry gives -BGV_E_EMPTY_AGGREGATE, zero bits and its n_bits.  Signature,
+ * count and field are read in one step: they always agree.
+ *
+ * bgv_sigpool_sum: the sum of entries, per group of 1 .. BGV_MAX_SUM_ENTRIES ids; reads entries and
+ * changes none.  Replaces SyncContributionAndProofPool's aggregate over the best contribution of
+ * each subnet (syncContributionAndProofPool.ts:169-187) and the EIP-7549 consolidation of one
+ * AttestationData's committee aggregates: one bgv_sigpool_get per entry (an inversion and a
+ * compression each) followed by bgv_aggregate_signatures over the bytes (a square root and a
+ * subgroup check each).  The device reads 288 B per entry and writes 96 B per group.
+ * -BGV_E_ARG and nothing written: ngroups > 65536, an n_ids of 0 or above BGV_MAX_SUM_ENTRIES, an
+ * id >= BGV_MAX_SIGPOOL, a needed pointer that is NULL (out_bits alone may be), out_bits with a
+ * bits_stride below ceil(sum of the group's n_bits / 8) for some group.  Per group:
+ *   an id not live  out_status -BGV_E_BAD_INDEX, every other output of the group zero
+ *   otherwise       out_count the sum of the entries' counts (a repeated id counts again);
+ *                   out_nbits the sum of their n_bits; out_bits + g * bits_stride the fields
+ *                   concatenated in list order at bit granularity, entry c at [off_c, off_c + n_c)
+ *                   with off_c the sum of the n_bits before it (a plain entry owns no position),
+ *                   the rest of the stride zero: the get_attesting_indices layout
+ *   count 0         out_status -BGV_E_EMPTY_AGGREGATE, out96 zero (bits and out_nbits as above)
+ *   count > 0       out_status 0, out96 the compressed G2 sum: byte for byte
+ *                   bgv_aggregate_signatures' over every signature held (the infinity encoding for
+ *                   a sum at infinity)
+ * An opened, empty entry contributes clear positions and no point (a subnet without contribution). */
+#define BGV_SIGPOOL_MAX_BITS 2048 /* MAX_VALIDATORS_PER_COMMITTEE */
+#define BGV_SIGPOOL_BITS_BYTES 256
+#define BGV_MAX_SUM_ENTRIES 64 /* = BGV_MAX_SET_COMMITTEES */
+enum { BGV_POOL_NOT_ADDED = 0, BGV_POOL_ADDED = 1, BGV_POOL_KNOWN = 2, BGV_POOL_OVERLAP = 3 };
+typedef struct {
+  uint32_t n_bits; /* the entry's */
+  uint32_t bit;    /* the single position, when bits == NULL */
+  const uint8_t* bits;
+} bgv_poolbits;
+typedef struct {
+  const uint32_t* ids;
+  uint32_t n_ids;
+} bgv_poolgroup;
+int bgv_sigpool_open_bits(bgv_ctx* ctx, uint32_t id, uint32_t n_bits);
+int bgv_verify_accumulate_bits(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets, size_t nsets,
+                               const bgv_pkspan* spans, int mode, const uint32_t* pool_of_set,
+                               const bgv_poolbits* bits_of_set, int32_t* out_job_codes, uint8_t* out_outcome,
+                               bgv_stats* stats);
+int bgv_verify_accumulate_bits_async(bgv_ctx* ctx, const bgv_job* jobs, size_t njobs, const bgv_set* sets,
+                                     size_t nsets, const bgv_pkspan* spans, int mode, const uint32_t* pool_of_set,
+                                     const bgv_poolbits* bits_of_set, int32_t* out_job_codes, uint8_t* out_outcome,
+                                     bgv_stats* stats, bgv_done_fn done, void* user);
+int bgv_sigpool_get_bits(bgv_ctx* ctx, const uint32_t* ids, size_t n, uint8_t* out96, uint32_t* out_count,
+                         int32_t* out_status, uint8_t* out_bits, uint32_t* out_nbits);
+int bgv_sigpool_sum(bgv_ctx* ctx, const bgv_poolgroup* groups, size_t ngroups, uint8_t* out96, uint32_t* out_count,
+                    int32_t* out_status, uint8_t* out_bits, size_t bits_stride, uint32_t* out_nbits);
 
 /* Deposit signature check (processDeposit.ts:62-70): key validated as above, then
  * Signature.fromBytes(sig, affine, true).verify(pk, signingRoot); any BLS error counts

@@ -183,9 +183,14 @@ struct SigPoolDev {
   uint32_t* d_gids = nullptr;  // bgv_sigpool_get: get_cap ids and their compressed sums
   uint8_t* d_gout = nullptr;
   size_t get_cap = 0;
-  Pinned<uint32_t> h_meta, h_gids;
+  uint32_t* d_sids = nullptr;  // bgv_sigpool_sum: sid_cap ids of written entries, group after group
+  size_t sid_cap = 0;
+  uint32_t* d_sfc = nullptr;   // first[sum_cap], count[sum_cap] of the groups the device answers
+  uint8_t* d_sout = nullptr;   // sum_cap x 96
+  size_t sum_cap = 0;
+  Pinned<uint32_t> h_meta, h_gids, h_sids, h_sfc;
   Pinned<int32_t> h_flag;
-  Pinned<uint8_t> h_gout;
+  Pinned<uint8_t> h_gout, h_sout;
 };
 
 // Device-resident committees (bgv_committee_put).  Every device keeps a directory of
@@ -264,6 +269,7 @@ struct CommitteeRec {
 
 struct Call;
 struct bgv_ctx;
+struct SigPoolFields;  // bgv_sigpool_bits_plan.h
 // One bgv_verify_aggregate or bgv_verify_accumulate call between its verdicts and its step on
 // device 0's utility stream (the context's aggregation worker runs the asynchronous ones).
 struct SigAggTask {
@@ -287,6 +293,8 @@ struct SigAggTask {
   int (*step)(const SigAggTask&) = nullptr;
   std::vector<uint32_t> gen_of_set;
   uint8_t* out_added = nullptr;
+  // bgv_verify_accumulate_bits: the submit's copy of bits_of_set, and out_outcome in out_added's place
+  std::shared_ptr<SigPoolFields> fields;
 };
 // What a super-batch's retry rounds need from its first pass.
 struct BatchState {
@@ -423,6 +431,10 @@ struct bgv_ctx {
   std::mutex pool_mu;
   std::vector<uint8_t> pool_live, pool_written;
   std::vector<uint32_t> pool_gen, pool_count;
+  // entries with participation bits: positions per id (0: a plain entry) and, allocated by the first
+  // bgv_sigpool_open_bits, BGV_MAX_SIGPOOL x BGV_SIGPOOL_BITS_BYTES of fields
+  std::vector<uint32_t> pool_nbits;
+  std::vector<uint8_t> pool_bits;
   std::atomic<uint64_t> sigpool_launches[2] = {};  // as sigagg_launches (bgv_debug_sigpool_launches)
   // dispatch
   std::vector<std::thread> dispatchers;

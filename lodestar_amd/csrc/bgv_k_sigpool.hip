@@ -7,6 +7,9 @@
 //   k_sigpool_get  one wavefront per requested entry: k_sigagg_sum's tail (the affine form with
 //                  the inversion on the whole wave, lane 0 compresses), the same field values as
 //                  bgv_aggregate_signatures' and so the same bytes
+//   k_sigpool_sum  one wavefront per group of up to 64 entries (bgv_sigpool_sum): lane j loads
+//                  entry j's accumulator, then k_sigpool_acc's tree and k_sigpool_get's tail; no
+//                  entry is written
 #include "bgv_device.h"
 #include "bgv_wfp.h"
 
@@ -74,7 +77,47 @@ __global__ void __launch_bounds__(64) k_sigpool_get(const uint32_t* __restrict__
   }
 }
 
+// One wavefront per group g: the sum of acc[ids[first[g] + j]], j < count[g] (1 .. BGV_WAVE entries,
+// every one written: the host's check).  Lane j takes entry j, the other lanes infinity; then
+// k_sigpool_acc's tree and k_sigpool_get's tail.  288 B read per entry, 96 B written per group.
+__global__ void __launch_bounds__(64) k_sigpool_sum(const uint32_t* __restrict__ ids, const uint32_t* __restrict__ first,
+                                                    const uint32_t* __restrict__ count, uint32_t ngroups,
+                                                    const g2_jac* __restrict__ acc, uint8_t* __restrict__ out96) {
+  extern __shared__ uint32_t lds[];
+  g2_jac* ls = reinterpret_cast<g2_jac*>(lds);
+  const uint32_t g = blockIdx.x, j = threadIdx.x;
+  if (g >= ngroups) return;  // grid.x = ngroups; the whole wave takes the same path
+  const uint32_t f = first[g], n = count[g];
+  g2_jac sum = j < n ? acc[ids[f + j]] : jac_infinity<fp2_t>();
+  for (uint32_t d = 1; d < BGV_WAVE; d <<= 1) {
+    ls[j] = sum;
+    __syncthreads();
+    if ((j & (2 * d - 1)) == 0) sum = jac_add(sum, ls[j + d]);
+    __syncthreads();
+  }
+  if (j == 0) ls[0] = sum;
+  __syncthreads();
+  sum = ls[0];
+  const fp_t ni = wfp_pow_fixed<BGV_POW_INV>(fp_add(fp_sqr(sum.z.c0), fp_sqr(sum.z.c1)));
+  const fp2_t zi = {fp_mul(sum.z.c0, ni), fp_neg(fp_mul(sum.z.c1, ni))};
+  const fp2_t zi2 = fp2_sqr(zi);
+  const g2_aff r = {fp2_mul(sum.x, zi2), fp2_mul(sum.y, fp2_mul(zi2, zi))};
+  if (j == 0) {
+    uint8_t b[96];
+    g2_compress(b, r, jac_is_inf(sum));
+    for (int q = 0; q < 96; ++q) out96[96ull * g + q] = b[q];
+  }
+}
+
 }  // extern "C"
+
+hipError_t bgv_launch_sigpool_sum(const uint32_t* ids, const uint32_t* first, const uint32_t* count, uint32_t ngroups,
+                                  const void* acc, uint8_t* out96, hipStream_t st) {
+  if (ngroups)
+    hipLaunchKernelGGL(k_sigpool_sum, dim3(ngroups), dim3(BGV_WAVE), BGV_WAVE * sizeof(g2_jac), st, ids, first, count,
+                       ngroups, reinterpret_cast<const g2_jac*>(acc), out96);
+  return hipGetLastError();
+}
 
 hipError_t bgv_launch_sigpool_acc(const uint32_t* ids, const uint32_t* first, const uint32_t* count,
                                   const uint32_t* fresh, uint32_t nentries, const void* pts, const int32_t* status,

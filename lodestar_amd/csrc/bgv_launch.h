@@ -187,6 +187,10 @@ hipError_t bgv_launch_sigpool_acc(const uint32_t* ids, const uint32_t* first, co
                                   void* acc, int32_t* flag, hipStream_t st);
 // out96[a] = acc[ids[a]], compressed; every named accumulator has been written
 hipError_t bgv_launch_sigpool_get(const uint32_t* ids, uint32_t n, const void* acc, uint8_t* out96, hipStream_t st);
+// out96[g] = the sum of acc[ids[first[g] + j]], j < count[g], compressed; 1 <= count[g] <= 64 and
+// every named accumulator has been written
+hipError_t bgv_launch_sigpool_sum(const uint32_t* ids, const uint32_t* first, const uint32_t* count, uint32_t ngroups,
+                                  const void* acc, uint8_t* out96, hipStream_t st);
 size_t bgv_fp12_bytes();
 hipError_t bgv_launch_fp12_bytes(const fp12_t* in, uint32_t n, uint8_t* out576, hipStream_t st);  // parity hooks
 hipError_t bgv_launch_partial(const bgv_dev_batch& b, uint32_t g0, uint32_t ng, void* scratch, uint8_t* out576,

@@ -41,6 +41,10 @@ SAMPLE_MAX_TRIES = 65536
 NO_AGG = 0xFFFFFFFF
 SIGAGG_WAVE_MAX = 2048  # BGV_SIGAGG_WAVE_MAX of include/blsgpu.h
 MAX_SIGPOOL = 16384  # BGV_MAX_SIGPOOL
+SIGPOOL_MAX_BITS = 2048  # BGV_SIGPOOL_MAX_BITS
+SIGPOOL_BITS_BYTES = 256  # BGV_SIGPOOL_BITS_BYTES
+MAX_SUM_ENTRIES = 64  # BGV_MAX_SUM_ENTRIES
+POOL_NOT_ADDED, POOL_ADDED, POOL_KNOWN, POOL_OVERLAP = 0, 1, 2, 3  # BGV_POOL_*
 
 EXPORTED_SYMBOLS = [
     "bgv_init", "bgv_close", "bgv_destroy", "bgv_pubkeys_put", "bgv_pubkeys_count", "bgv_verify",
@@ -55,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "bgv_verify_aggregate", "bgv_verify_aggregate_async", "bgv_debug_sigagg_launches",
     "bgv_sigpool_open", "bgv_sigpool_drop_range", "bgv_sigpool_get", "bgv_verify_accumulate",
     "bgv_verify_accumulate_async", "bgv_debug_sigpool_launches",
+    "bgv_sigpool_open_bits", "bgv_verify_accumulate_bits", "bgv_verify_accumulate_bits_async",
+    "bgv_sigpool_get_bits", "bgv_sigpool_sum",
 ]
 
 
@@ -76,6 +82,14 @@ class BgvPkBits(ctypes.Structure):
 class BgvPkSpan(ctypes.Structure):
     _fields_ = [("committees", ctypes.c_void_p), ("n_committees", ctypes.c_uint32), ("n_bits", ctypes.c_uint32),
                 ("bits", ctypes.c_void_p)]
+
+
+class BgvPoolBits(ctypes.Structure):
+    _fields_ = [("n_bits", ctypes.c_uint32), ("bit", ctypes.c_uint32), ("bits", ctypes.c_void_p)]
+
+
+class BgvPoolGroup(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("n_ids", ctypes.c_uint32)]
 
 
 class BgvJob(ctypes.Structure):
@@ -161,6 +175,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "bgv_verify_accumulate": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P], ctypes.c_int),
             "bgv_verify_accumulate_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P, DONE_FN, P], ctypes.c_int),
             "bgv_debug_sigpool_launches": ([P, P], ctypes.c_int),
+            "bgv_sigpool_open_bits": ([P, U32, U32], ctypes.c_int),
+            "bgv_verify_accumulate_bits": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P, P], ctypes.c_int),
+            "bgv_verify_accumulate_bits_async": ([P, P, SZ, P, SZ, P, ctypes.c_int, P, P, P, P, P, DONE_FN, P],
+                                                 ctypes.c_int),
+            "bgv_sigpool_get_bits": ([P, P, SZ, P, P, P, P, P], ctypes.c_int),
+            "bgv_sigpool_sum": ([P, P, SZ, P, P, P, P, SZ, P], ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if name in ("bgv_debug_prepare", "bgv_debug_uniform", "bgv_set_split", "bgv_committee_put",
@@ -172,7 +192,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                         "bgv_verify_aggregate", "bgv_verify_aggregate_async",
                         "bgv_debug_sigagg_launches", "bgv_sigpool_open", "bgv_sigpool_drop_range",
                         "bgv_sigpool_get", "bgv_verify_accumulate", "bgv_verify_accumulate_async",
-                        "bgv_debug_sigpool_launches") and path != os.path.join(HERE, "libblsgpu.so") and \
+                        "bgv_debug_sigpool_launches", "bgv_sigpool_open_bits", "bgv_verify_accumulate_bits",
+                        "bgv_verify_accumulate_bits_async", "bgv_sigpool_get_bits",
+                        "bgv_sigpool_sum") and path != os.path.join(HERE, "libblsgpu.so") and \
                     not hasattr(lib, name):
                 continue  # parity hook absent from an older A/B build (tools/gpu/ab.sh)
             fn = getattr(lib, name)
@@ -562,9 +584,14 @@ class Context:
         return PendingAggregate(self, packed, agg_of_set, naggs, mode)
 
     # --- device-resident signature pools (bgv_sigpool_open) --------------------
-    def sigpool_open(self, pool_id: int):
-        """Open pool entry pool_id (0 .. MAX_SIGPOOL - 1): a G2 accumulator, empty, with a count."""
-        _check(self.lib.bgv_sigpool_open(self._h, pool_id))
+    def sigpool_open(self, pool_id: int, n_bits: int = 0):
+        """Open pool entry pool_id (0 .. MAX_SIGPOOL - 1): a G2 accumulator, empty, with a count;
+        with n_bits (1 .. SIGPOOL_MAX_BITS) also a participation field of that many positions, all
+        clear (bgv_sigpool_open_bits)."""
+        if n_bits:
+            _check(self.lib.bgv_sigpool_open_bits(self._h, pool_id, n_bits))
+        else:
+            _check(self.lib.bgv_sigpool_open(self._h, pool_id))
 
     def sigpool_drop_range(self, first_id: int, count: int) -> int:
         """Drop the live entries of ids first_id .. first_id + count - 1; returns how many."""
@@ -604,6 +631,70 @@ class Context:
         if len(pool_of_set) != packed.nsets:
             raise ValueError("pool_of_set takes one entry per set")
         return PendingAccumulate(self, packed, pool_of_set, mode)
+
+    def verify_accumulate_bits(self, jobs, pool_of_set: Sequence[int], bits_of_set, mode: int = MODE_WORKER,
+                               stats: Optional[BgvStats] = None):
+        """bgv_verify_accumulate_bits: verify_accumulate into entries that hold participation bits.
+        bits_of_set is None (no entry with bits is tagged) or one item per set: None (the set's
+        entry is plain, or the set is untagged), (n_bits, position) for a single member or (n_bits,
+        field bytes) in SSZ bit order.  Returns (codes, outcome) with outcome[i] one of POOL_*."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(pool_of_set) != packed.nsets:
+            raise ValueError("pool_of_set takes one entry per set")
+        njobs = len(packed.jobs_in)
+        out = (ctypes.c_int32 * max(1, njobs))()
+        tags = (ctypes.c_uint32 * max(1, packed.nsets))(*pool_of_set)
+        bits, _keep = pack_poolbits(bits_of_set, packed.nsets)
+        outcome = (ctypes.c_uint8 * max(1, packed.nsets))()
+        st = ctypes.byref(stats) if stats is not None else None
+        _check(self.lib.bgv_verify_accumulate_bits(self._h, packed.jobs, njobs, packed.sets, packed.nsets,
+                                                   packed.as_spans(), mode, tags, bits, out, outcome, st))
+        return list(out[:njobs]), list(outcome[:packed.nsets])
+
+    def verify_accumulate_bits_async(self, jobs, pool_of_set: Sequence[int], bits_of_set, mode: int = MODE_WORKER):
+        """bgv_verify_accumulate_bits_async: returns a PendingAccumulate whose wait() gives what
+        verify_accumulate_bits returns."""
+        packed = jobs if isinstance(jobs, PackedCall) else PackedCall(jobs)
+        if len(pool_of_set) != packed.nsets:
+            raise ValueError("pool_of_set takes one entry per set")
+        return PendingAccumulate(self, packed, pool_of_set, mode, bits_of_set=bits_of_set, with_bits=True)
+
+    def sigpool_get_bits(self, ids: Sequence[int]):
+        """bgv_sigpool_get_bits: [(status, count, compressed96, n_bits, field)] per id, field being
+        the ceil(n_bits / 8) bytes of the entry's positions (b"" for a plain or not-live entry)."""
+        n = len(ids)
+        arr = (ctypes.c_uint32 * max(1, n))(*ids)
+        out = ctypes.create_string_buffer(96 * max(1, n))
+        cnt = (ctypes.c_uint32 * max(1, n))()
+        st = (ctypes.c_int32 * max(1, n))()
+        bits = ctypes.create_string_buffer(SIGPOOL_BITS_BYTES * max(1, n))
+        nb = (ctypes.c_uint32 * max(1, n))()
+        _check(self.lib.bgv_sigpool_get_bits(self._h, arr, n, out, cnt, st, bits, nb))
+        return [(st[k], cnt[k], out.raw[96 * k:96 * k + 96], nb[k],
+                 bits.raw[SIGPOOL_BITS_BYTES * k:SIGPOOL_BITS_BYTES * k + (nb[k] + 7) // 8]) for k in range(n)]
+
+    def sigpool_sum(self, groups: Sequence[Sequence[int]], with_bits: bool = True, bits_stride: Optional[int] = None):
+        """bgv_sigpool_sum: per group of entry ids [(status, count, compressed96, n_bits, field)],
+        the G2 sum of the entries and their fields concatenated in list order; entries unchanged.
+        with_bits=False passes no bits buffer (n_bits is still returned, field is b"").  The stride
+        defaults to the largest a group of its length can need."""
+        ng = len(groups)
+        arrs = [(ctypes.c_uint32 * max(1, len(g)))(*g) for g in groups]
+        gs = (BgvPoolGroup * max(1, ng))()
+        for k, g in enumerate(groups):
+            gs[k].ids = ctypes.cast(arrs[k], ctypes.c_void_p)
+            gs[k].n_ids = len(g)
+        if bits_stride is None:
+            bits_stride = SIGPOOL_BITS_BYTES * max([1] + [min(len(g), MAX_SUM_ENTRIES) for g in groups])
+        out = ctypes.create_string_buffer(96 * max(1, ng))
+        cnt = (ctypes.c_uint32 * max(1, ng))()
+        st = (ctypes.c_int32 * max(1, ng))()
+        nb = (ctypes.c_uint32 * max(1, ng))()
+        bits = ctypes.create_string_buffer(max(1, bits_stride * ng)) if with_bits else None
+        _check(self.lib.bgv_sigpool_sum(self._h, gs, ng, out, cnt, st, bits, bits_stride, nb))
+        return [(st[k], cnt[k], out.raw[96 * k:96 * k + 96], nb[k],
+                 bits.raw[bits_stride * k:bits_stride * k + (nb[k] + 7) // 8] if with_bits else b"")
+                for k in range(ng)]
 
     def sigpool_launches(self):
         """bgv_debug_sigpool_launches (parity hook): accumulation steps launched so far with the
@@ -692,7 +783,8 @@ class PendingAccumulate:
     """One bgv_verify_accumulate_async call: keeps its buffers alive until done() has fired on the
     context's worker thread, where the outputs are read."""
 
-    def __init__(self, ctx: "Context", packed: "PackedCall", pool_of_set: Sequence[int], mode: int):
+    def __init__(self, ctx: "Context", packed: "PackedCall", pool_of_set: Sequence[int], mode: int,
+                 bits_of_set=None, with_bits: bool = False):
         self._packed = packed
         njobs, nsets = len(packed.jobs_in), packed.nsets
         self._out = (ctypes.c_int32 * max(1, njobs))()
@@ -705,10 +797,17 @@ class PendingAccumulate:
 
         def done(_user, rc):
             self._rc = rc
-            self._result = (list(self._out[:njobs]), [bool(a) for a in self._added[:nsets]])
+            self._result = (list(self._out[:njobs]),
+                            list(self._added[:nsets]) if with_bits else [bool(a) for a in self._added[:nsets]])
             self._event.set()
 
         self._done = DONE_FN(done)
+        if with_bits:  # the fields are copied at submit: nothing of them is kept here
+            bits, _keep = pack_poolbits(bits_of_set, nsets)
+            _check(ctx.lib.bgv_verify_accumulate_bits_async(ctx.handle, packed.jobs, njobs, packed.sets, nsets,
+                                                            packed.as_spans(), mode, self._tags, bits, self._out,
+                                                            self._added, ctypes.byref(self.stats), self._done, None))
+            return
         _check(ctx.lib.bgv_verify_accumulate_async(ctx.handle, packed.jobs, njobs, packed.sets, nsets,
                                                    packed.as_spans(), mode, self._tags, self._out, self._added,
                                                    ctypes.byref(self.stats), self._done, None))
@@ -718,6 +817,29 @@ class PendingAccumulate:
             raise TimeoutError("bgv_verify_accumulate_async: done() has not fired")
         _check(self._rc)
         return self._result
+
+
+def pack_poolbits(bits_of_set, nsets: int):
+    """bits_of_set (Context.verify_accumulate_bits) as a bgv_poolbits array, or None; the second
+    value keeps the field buffers alive."""
+    if bits_of_set is None:
+        return None, None
+    if len(bits_of_set) != nsets:
+        raise ValueError("bits_of_set takes one entry per set")
+    arr = (BgvPoolBits * max(1, nsets))()
+    keep = []
+    for k, item in enumerate(bits_of_set):
+        if item is None:
+            continue
+        n_bits, member = item
+        arr[k].n_bits = n_bits
+        if isinstance(member, int):
+            arr[k].bit = member
+        else:
+            buf = ctypes.create_string_buffer(bytes(member), max(1, len(member)))
+            keep.append(buf)
+            arr[k].bits = ctypes.cast(buf, ctypes.c_void_p)
+    return arr, keep
 
 
 class SetSpec:

@@ -328,19 +328,41 @@ class BlsGpuVerifier {
     return (await this._sameMessage(sets, message, opts, false, poolId)).results;
   }
 
-  async _sameMessage(sets, message, opts, aggregate, pool) {
+  /**
+   * verifyAndPoolSameMessage into an entry that holds participation bits (poolOpen(id, {nBits});
+   * bgv_verify_accumulate_bits).  Each set is {publicKey, signature} with `bit` (its position in the
+   * entry) or `bits` (its field, a Uint8Array of ceil(nBits / 8) bytes in SSZ bit order);
+   * opts.nBits is the entry's size.  Resolves to one {valid, outcome} per set: `valid` is the
+   * verdict (a known attestation is still a valid gossip message) and `outcome` what the entry did
+   * with it: "added" (InsertOutcome.NewData / Aggregated), "known" (AlreadyKnown), "overlap"
+   * (NotBetterThan: it shares some position with the entry and brings others), or null when the
+   * set was not valid or the entry was dropped meanwhile.  Bits and signature change in one step
+   * on the device side, so the pool keeps neither (INTEGRATION.md §2e).
+   */
+  async verifyAndPoolBitsSameMessage(sets, message, poolId, opts = {}) {
+    const members = sets.map((s) =>
+      s.bits !== undefined ? {poolNBits: opts.nBits, poolBits: s.bits} : {poolNBits: opts.nBits, poolBit: s.bit}
+    );
+    return (await this._sameMessage(sets, message, opts, false, poolId, members)).results;
+  }
+
+  async _sameMessage(sets, message, opts, aggregate, pool, members) {
     if (this.pendingRuns.length || this.flushing) await this.flushPubkeys();
     if (sets.length === 0) return {results: [], signature: null};
     const native = sets.map((s) =>
       toNativeSet({type: SignatureSetType.single, pubkey: s.publicKey, signingRoot: message, signature: s.signature})
     );
     // one unit in the buffer and one device call, whatever its size; each set its own job there
-    return this.queueBlsWork({opts: {...opts, batchable: true}, sets: native, perSet: true, aggregate, pool});
+    return this.queueBlsWork({opts: {...opts, batchable: true}, sets: native, perSet: true, aggregate, pool, members});
   }
 
-  /** Opens the device-resident signature pool entry `id` (0..16383), empty (INTEGRATION.md §2e). */
-  poolOpen(id) {
-    addon.sigpoolOpen(this.ctx, id);
+  /**
+   * Opens the device-resident signature pool entry `id` (0..16383), empty (INTEGRATION.md §2e);
+   * with opts.nBits (1..2048) it also holds a participation field of that many positions, all clear.
+   */
+  poolOpen(id, opts = {}) {
+    if (opts.nBits) addon.sigpoolOpenBits(this.ctx, id, opts.nBits);
+    else addon.sigpoolOpen(this.ctx, id);
   }
 
   /** Drops the live entries of ids first .. first + count - 1 (a pruned slot's); returns how many. */
@@ -361,6 +383,31 @@ class BlsGpuVerifier {
       count: count[k],
       signature: status[k] === 0 ? sigs.slice(96 * k, 96 * k + 96) : null,
     }));
+  }
+
+  /**
+   * poolGet plus the entry's participation field: per id {status, count, signature, nBits, bits},
+   * bits a Uint8Array of ceil(nBits / 8) bytes (nBits 0 for an entry without bits or not open).
+   * Signature, count and bits are read in one step.
+   */
+  async poolGetBits(ids) {
+    const arr = ids instanceof Uint32Array ? ids : Uint32Array.from(ids);
+    const r = await addon.sigpoolGetBits(this.ctx, arr);
+    return Array.from(arr, (_, k) => poolRecord(r, k));
+  }
+
+  /**
+   * Sums entries on the device, off the event loop (bgv_sigpool_sum): `groups` is a list of id
+   * lists (1..64 ids each); per group {status, count, signature|null, bits, nBits} with the
+   * entries' fields concatenated in list order -- SyncContributionAndProofPool's getSyncAggregate
+   * over the subnets' best contributions, or the EIP-7549 on-chain attestation of one
+   * AttestationData over its committees.  No entry changes.
+   */
+  async poolSum(groups) {
+    const lengths = Uint32Array.from(groups, (g) => g.length);
+    const ids = Uint32Array.from([].concat(...groups.map((g) => Array.from(g))));
+    const r = await addon.sigpoolSum(this.ctx, ids, lengths);
+    return groups.map((_, k) => poolRecord(r, k));
   }
 
   /** IBlsVerifier.canAcceptWork: false while the sets queued or in flight reach opts.maxInflightSigs. */
@@ -536,6 +583,7 @@ class BlsGpuVerifier {
     const nativeJobs = [];
     let naggs = 0;
     let pooled = false;
+    let withBits = false; // a run holds one kind of caller: every pool caller of this call has members
     let nsets = 0;
     for (const job of jobs) {
       const w = job.workReq;
@@ -549,11 +597,19 @@ class BlsGpuVerifier {
       job.agg = w.aggregate ? naggs++ : -1;
       const tag = w.pool !== undefined ? {pool: w.pool} : job.agg >= 0 ? {agg: job.agg} : null;
       pooled = pooled || w.pool !== undefined;
-      for (const s of w.sets) nativeJobs.push({sets: [tag ? {...s, ...tag} : s], batchable: true});
+      withBits = withBits || w.members !== undefined;
+      w.sets.forEach((s, k) =>
+        nativeJobs.push({sets: [tag ? {...s, ...tag, ...(w.members ? w.members[k] : null)} : s], batchable: true})
+      );
     }
     try {
-      let codes, aggs, added;
-      if (pooled) {
+      let codes, aggs, added, outcome;
+      if (withBits) {
+        const res = await addon.verifyAccumulateBits(this.ctx, nativeJobs, 0);
+        codes = res.codes;
+        codes.stats = res.stats;
+        outcome = res.outcome;
+      } else if (pooled) {
         const res = await addon.verifyAccumulate(this.ctx, nativeJobs, 0);
         codes = res.codes;
         codes.stats = res.stats;
@@ -573,6 +629,15 @@ class BlsGpuVerifier {
         if (w.perSet) {
           // per set: an error code is false for that set (the interface's per-set retry), never a rejection
           const inPool = w.pool !== undefined;
+          if (w.members !== undefined) {
+            const results = w.sets.map((_, k) => ({
+              valid: codes[job.first + k] === 1,
+              outcome: POOL_OUTCOME[outcome[job.firstSet + k]],
+            }));
+            w.sets.forEach((_, k) => (codes[job.first + k] < 0 ? errorCount++ : successCount++));
+            job.resolve({results, signature: null});
+            return;
+          }
           const results = w.sets.map((_, k) => codes[job.first + k] === 1 && (!inPool || added[job.firstSet + k] === 1));
           w.sets.forEach((_, k) => (codes[job.first + k] < 0 ? errorCount++ : successCount++));
           const ok = job.agg >= 0 && aggs.status[job.agg] === 0;
@@ -666,9 +731,24 @@ class BlsGpuVerifier {
   }
 }
 
-// which kind of same-message caller a unit of work is: "pool", "aggregate" or null
+// which kind of same-message caller a unit of work is: "poolbits", "pool", "aggregate" or null
 function callerKind(w) {
-  return w.pool !== undefined ? "pool" : w.aggregate ? "aggregate" : null;
+  return w.members !== undefined ? "poolbits" : w.pool !== undefined ? "pool" : w.aggregate ? "aggregate" : null;
+}
+
+// BGV_POOL_NOT_ADDED, _ADDED, _KNOWN, _OVERLAP
+const POOL_OUTCOME = [null, "added", "known", "overlap"];
+
+// entry or group k of a sigpoolGetBits / sigpoolSum result
+function poolRecord(r, k) {
+  const nBits = r.nBits[k];
+  return {
+    status: r.status[k],
+    count: r.count[k],
+    signature: r.status[k] === 0 ? r.sigs.slice(96 * k, 96 * k + 96) : null,
+    nBits,
+    bits: r.bits.slice(r.stride * k, r.stride * k + ((nBits + 7) >> 3)),
+  };
 }
 
 function unwrap(code) {

@@ -25,6 +25,10 @@
  *          -> Promise<{codes, stats, added: Uint8Array}>   (bgv_verify_accumulate_async)
  *   sigpoolOpen(ctx, id), sigpoolDropRange(ctx, firstId, count) -> number
  *   sigpoolGet(ctx, ids: Uint32Array) -> Promise<{status, count, sigs}>  (on a libuv pool thread)
+ *   sigpoolOpenBits(ctx, id, nBits); verifyAccumulateBits(ctx, jobs, mode) -> Promise<{codes, stats,
+ *          outcome: Uint8Array}>   (bgv_verify_accumulate_bits_async)
+ *   sigpoolGetBits(ctx, ids) / sigpoolSum(ctx, ids, lengths) -> Promise<{status, count, sigs, bits,
+ *          nBits, stride}>  (on a libuv pool thread)
  *   strerror(code) -> string
  *   close(ctx)
  * SURVEY 8(f) entry points and parity hooks (synchronous):
@@ -125,9 +129,11 @@ typedef struct {
   napi_ref* refs; /* keep every input buffer alive until completion */
   size_t nrefs;
   /* verifyAggregate (1): the sets' `agg` tags beside sets, and the aggregates' outputs;
-   * verifyAccumulate (2): the sets' `pool` tags in tags, and per set whether it was added */
+   * verifyAccumulate (2): the sets' `pool` tags in tags, and per set whether it was added;
+   * verifyAccumulateBits (3): as 2 with the sets' positions in poolbits, and per set its outcome */
   int aggregate;
   uint8_t* added;
+  bgv_poolbits* poolbits;
   uint32_t* tags;
   size_t naggs;
   uint8_t* agg96;
@@ -432,6 +438,21 @@ static napi_value js_sigpool_open(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* sigpoolOpenBits(ctx, id, nBits): bgv_sigpool_open_bits */
+static napi_value js_sigpool_open_bits(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint32_t id = 0, nbits = 0;
+  if (argc < 3 || napi_get_value_uint32(env, argv[1], &id) != napi_ok ||
+      napi_get_value_uint32(env, argv[2], &nbits) != napi_ok)
+    return throw_code(env, -BGV_E_ARG);
+  int rc = bgv_sigpool_open_bits(ctx, id, nbits);
+  if (rc) return throw_code(env, rc);
+  return NULL;
+}
+
 static napi_value js_sigpool_drop_range(napi_env env, napi_callback_info info) {
   size_t argc = 3;
   napi_value argv[3], out;
@@ -449,7 +470,8 @@ static napi_value js_sigpool_drop_range(napi_env env, napi_callback_info info) {
 
 /* sigpoolGet(ctx, ids: Uint32Array) -> Promise<{status: Int32Array, count: Uint32Array, sigs:
  * Uint8Array (n x 96 compressed)}>: bgv_sigpool_get on a libuv pool thread (it waits for the
- * device); rejects with an Error whose .bgvCode is the negative library code. */
+ * device); rejects with an Error whose .bgvCode is the negative library code.  sigpoolGetBits and
+ * sigpoolSum share the request and its two callbacks. */
 typedef struct {
   napi_async_work work;
   napi_deferred deferred;
@@ -461,12 +483,24 @@ typedef struct {
   uint32_t* count;
   int32_t* status;
   int rc;
+  /* sigpoolGetBits (kind 1): the fields and n_bits; sigpoolSum (kind 2): n is the number of groups,
+   * ids the groups' ids one after the other, groups their lists, stride the bytes per group in bits */
+  int kind;
+  uint8_t* bits;
+  uint32_t* nbits;
+  bgv_poolgroup* groups;
+  size_t stride;
 } pool_get_req;
 
 static void pool_get_execute(napi_env env, void* data) {
   (void)env;
   pool_get_req* r = (pool_get_req*)data;
-  r->rc = bgv_sigpool_get(r->c, r->ids, r->n, r->out96, r->count, r->status);
+  if (r->kind == 2)
+    r->rc = bgv_sigpool_sum(r->c, r->groups, r->n, r->out96, r->count, r->status, r->bits, r->stride, r->nbits);
+  else if (r->kind == 1)
+    r->rc = bgv_sigpool_get_bits(r->c, r->ids, r->n, r->out96, r->count, r->status, r->bits, r->nbits);
+  else
+    r->rc = bgv_sigpool_get(r->c, r->ids, r->n, r->out96, r->count, r->status);
 }
 
 static void pool_get_complete(napi_env env, napi_status status, void* data) {
@@ -483,6 +517,18 @@ static void pool_get_complete(napi_env env, napi_status status, void* data) {
     sigs = new_bytes(env, 96 * r->n, &dst);
     if (r->n) memcpy(dst, r->out96, 96 * r->n);
     napi_set_named_property(env, out, "sigs", sigs);
+    if (r->kind) { /* bits: n x stride bytes, nBits: Uint32Array, stride */
+      napi_value bits, nab, narr, sv;
+      bits = new_bytes(env, r->stride * r->n, &dst);
+      if (r->n) memcpy(dst, r->bits, r->stride * r->n);
+      napi_set_named_property(env, out, "bits", bits);
+      napi_create_arraybuffer(env, 4 * r->n, &dst, &nab);
+      if (r->n) memcpy(dst, r->nbits, 4 * r->n);
+      napi_create_typedarray(env, napi_uint32_array, r->n, nab, 0, &narr);
+      napi_set_named_property(env, out, "nBits", narr);
+      napi_create_uint32(env, (uint32_t)r->stride, &sv);
+      napi_set_named_property(env, out, "stride", sv);
+    }
     napi_resolve_deferred(env, r->deferred, out);
   } else {
     const int rc = status == napi_ok ? r->rc : -BGV_E_ARG;
@@ -499,10 +545,16 @@ static void pool_get_complete(napi_env env, napi_status status, void* data) {
   free(r->out96);
   free(r->count);
   free(r->status);
+  free(r->bits);
+  free(r->nbits);
+  free(r->groups);
   free(r);
 }
 
-static napi_value js_sigpool_get(napi_env env, napi_callback_info info) {
+/* sigpoolGet(ctx, ids) and, kind 1, sigpoolGetBits(ctx, ids) -> Promise<{status, count, sigs, bits:
+ * Uint8Array (n x stride), nBits: Uint32Array, stride: BGV_SIGPOOL_BITS_BYTES}>
+ * (bgv_sigpool_get_bits), on a libuv pool thread like sigpoolGet */
+static napi_value sigpool_get_start(napi_env env, napi_callback_info info, int kind) {
   size_t argc = 2;
   napi_value argv[2], promise, name;
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
@@ -523,9 +575,77 @@ static napi_value js_sigpool_get(napi_env env, napi_callback_info info) {
   r->out96 = (uint8_t*)calloc(r->n ? r->n : 1, 96);
   r->count = (uint32_t*)calloc(r->n ? r->n : 1, sizeof(uint32_t));
   r->status = (int32_t*)calloc(r->n ? r->n : 1, sizeof(int32_t));
+  r->kind = kind;
+  if (kind) {
+    r->stride = BGV_SIGPOOL_BITS_BYTES;
+    r->bits = (uint8_t*)calloc(r->n ? r->n : 1, BGV_SIGPOOL_BITS_BYTES);
+    r->nbits = (uint32_t*)calloc(r->n ? r->n : 1, sizeof(uint32_t));
+  }
   if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
       napi_create_reference(env, argv[0], 1, &r->ctx_ref) != napi_ok ||
       napi_create_string_utf8(env, "blsgpu.sigpoolGet", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, pool_get_execute, pool_get_complete, r, &r->work) != napi_ok ||
+      napi_queue_async_work(env, r->work) != napi_ok) {
+    napi_throw_error(env, NULL, "blsgpu: N-API failure");
+    return NULL;
+  }
+  return promise;
+}
+
+static napi_value js_sigpool_get(napi_env env, napi_callback_info info) { return sigpool_get_start(env, info, 0); }
+static napi_value js_sigpool_get_bits(napi_env env, napi_callback_info info) { return sigpool_get_start(env, info, 1); }
+
+/* sigpoolSum(ctx, ids: Uint32Array, lengths: Uint32Array) -> Promise<{status, count, sigs, bits, nBits,
+ * stride}>: bgv_sigpool_sum over lengths.length groups, group g being the next lengths[g] ids; on a
+ * libuv pool thread.  stride is BGV_SIGPOOL_BITS_BYTES times the longest group (at most
+ * BGV_MAX_SUM_ENTRIES), which every group's field fits. */
+static napi_value js_sigpool_sum(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], promise, name;
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  OPEN_CTX(env, argv[0], ctx);
+  uint8_t *ids, *lens;
+  size_t ilen, llen;
+  napi_typedarray_type ti = napi_uint8_array, tl = napi_uint8_array;
+  bool ta_i = false, ta_l = false;
+  if (argc < 3) return throw_code(env, -BGV_E_ARG);
+  napi_is_typedarray(env, argv[1], &ta_i);
+  napi_is_typedarray(env, argv[2], &ta_l);
+  if (ta_i) napi_get_typedarray_info(env, argv[1], &ti, NULL, NULL, NULL, NULL);
+  if (ta_l) napi_get_typedarray_info(env, argv[2], &tl, NULL, NULL, NULL, NULL);
+  if (!ta_i || !ta_l || ti != napi_uint32_array || tl != napi_uint32_array || get_bytes(env, argv[1], &ids, &ilen) ||
+      get_bytes(env, argv[2], &lens, &llen))
+    return throw_code(env, -BGV_E_ARG);
+  const size_t ng = llen / 4, ni = ilen / 4;
+  size_t total = 0, longest = 1;
+  for (size_t g = 0; g < ng; ++g) {
+    const uint32_t l = ((const uint32_t*)lens)[g];
+    if (l == 0 || l > BGV_MAX_SUM_ENTRIES) return throw_code(env, -BGV_E_ARG);
+    total += l;
+    if (l > longest) longest = l;
+  }
+  if (total != ni || ng > 65536) return throw_code(env, -BGV_E_ARG);
+  pool_get_req* r = (pool_get_req*)calloc(1, sizeof(pool_get_req));
+  r->c = ctx;
+  r->kind = 2;
+  r->n = ng;
+  r->ids = (uint32_t*)calloc(ni ? ni : 1, sizeof(uint32_t)); /* a copy: the caller may reuse its arrays */
+  if (ni) memcpy(r->ids, ids, 4 * ni);
+  r->groups = (bgv_poolgroup*)calloc(ng ? ng : 1, sizeof(bgv_poolgroup));
+  for (size_t g = 0, at = 0; g < ng; ++g) {
+    r->groups[g].ids = r->ids + at;
+    r->groups[g].n_ids = ((const uint32_t*)lens)[g];
+    at += r->groups[g].n_ids;
+  }
+  r->stride = BGV_SIGPOOL_BITS_BYTES * longest;
+  r->out96 = (uint8_t*)calloc(ng ? ng : 1, 96);
+  r->count = (uint32_t*)calloc(ng ? ng : 1, sizeof(uint32_t));
+  r->status = (int32_t*)calloc(ng ? ng : 1, sizeof(int32_t));
+  r->bits = (uint8_t*)calloc(ng ? ng : 1, r->stride);
+  r->nbits = (uint32_t*)calloc(ng ? ng : 1, sizeof(uint32_t));
+  if (napi_create_promise(env, &r->deferred, &promise) != napi_ok ||
+      napi_create_reference(env, argv[0], 1, &r->ctx_ref) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu.sigpoolSum", NAPI_AUTO_LENGTH, &name) != napi_ok ||
       napi_create_async_work(env, NULL, name, pool_get_execute, pool_get_complete, r, &r->work) != napi_ok ||
       napi_queue_async_work(env, r->work) != napi_ok) {
     napi_throw_error(env, NULL, "blsgpu: N-API failure");
@@ -925,6 +1045,7 @@ static void free_req_heap(verify_req* r) {
   free(r->agg_status);
   free(r->agg_count);
   free(r->added);
+  free(r->poolbits);
   free(r);
 }
 
@@ -972,10 +1093,10 @@ static void settle(napi_env env, verify_req* r) {
   napi_create_object(env, &res);
   napi_set_named_property(env, res, "codes", arr);
   napi_set_named_property(env, res, "stats", st);
-  if (r->aggregate == 2) {
+  if (r->aggregate >= 2) {
     napi_value added = new_bytes(env, r->nsets, &dst);
     if (r->nsets) memcpy(dst, r->added, r->nsets);
-    napi_set_named_property(env, res, "added", added);
+    napi_set_named_property(env, res, r->aggregate == 3 ? "outcome" : "added", added);
     napi_resolve_deferred(env, r->deferred, res);
     return;
   }
@@ -1050,7 +1171,11 @@ static void addon_finalize(napi_env env, void* data, void* hint) {
  * job is accepted; bgv_verify_aggregate), to {codes, stats, aggs: {status, count, sigs}} with one
  * entry per aggregate 0 .. the largest agg given; verifyAccumulate(ctx, jobs, mode), whose sets may
  * carry `pool: number` (the open signature pool entry the set's signature is added to when its job
- * is accepted; bgv_verify_accumulate), to {codes, stats, added: Uint8Array (1 per set that was added)} */
+ * is accepted; bgv_verify_accumulate), to {codes, stats, added: Uint8Array (1 per set that was added)};
+ * verifyAccumulateBits(ctx, jobs, mode), whose sets carry `pool` and, for an entry with bits,
+ * `poolNBits` with `poolBit` (the set's position) or `poolBits` (its field, a Uint8Array of
+ * ceil(poolNBits / 8) bytes; bgv_verify_accumulate_bits), to {codes, stats, outcome: Uint8Array
+ * (BGV_POOL_* per set)} */
 static napi_value verify_start(napi_env env, napi_callback_info info, int aggregate) {
   size_t argc = 3;
   napi_value argv[3];
@@ -1081,6 +1206,7 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
   r->pkbits = (bgv_pkbits*)calloc(cap, sizeof(bgv_pkbits));
   r->spans = (bgv_pkspan*)calloc(cap, sizeof(bgv_pkspan));
   r->tags = (uint32_t*)calloc(cap, sizeof(uint32_t));
+  if (aggregate == 3) r->poolbits = (bgv_poolbits*)calloc(cap, sizeof(bgv_poolbits));
   size_t refcap = 256;
   r->refs = (napi_ref*)calloc(refcap, sizeof(napi_ref));
   for (uint32_t j = 0; j < njobs; ++j) {
@@ -1102,6 +1228,7 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
         r->pkbits = (bgv_pkbits*)realloc(r->pkbits, cap * sizeof(bgv_pkbits));
         r->spans = (bgv_pkspan*)realloc(r->spans, cap * sizeof(bgv_pkspan));
         r->tags = (uint32_t*)realloc(r->tags, cap * sizeof(uint32_t));
+        if (aggregate == 3) r->poolbits = (bgv_poolbits*)realloc(r->poolbits, cap * sizeof(bgv_poolbits));
       }
       if (r->nrefs + 4 > refcap) {
         refcap *= 2;
@@ -1128,12 +1255,39 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
       memset(&r->spans[r->nsets], 0, sizeof(bgv_pkspan));
       r->tags[r->nsets] = BGV_NO_AGG;
       bool tagged = false;
-      if (aggregate) napi_has_named_property(env, s, aggregate == 2 ? "pool" : "agg", &tagged);
+      if (aggregate) napi_has_named_property(env, s, aggregate >= 2 ? "pool" : "agg", &tagged);
+      if (aggregate == 3) { /* poolNBits with poolBit (one position) or poolBits (a field; the library copies it) */
+        bgv_poolbits* pq = &r->poolbits[r->nsets];
+        bool has_n = false, has_bit = false, has_bits = false;
+        memset(pq, 0, sizeof(*pq));
+        napi_has_named_property(env, s, "poolNBits", &has_n);
+        napi_has_named_property(env, s, "poolBit", &has_bit);
+        napi_has_named_property(env, s, "poolBits", &has_bits);
+        if (has_n) {
+          napi_value nv, bv;
+          uint8_t* bd;
+          size_t bl;
+          int bad = napi_get_named_property(env, s, "poolNBits", &nv) != napi_ok ||
+                    napi_get_value_uint32(env, nv, &pq->n_bits) != napi_ok || has_bit == has_bits;
+          if (!bad && has_bit)
+            bad = napi_get_named_property(env, s, "poolBit", &bv) != napi_ok ||
+                  napi_get_value_uint32(env, bv, &pq->bit) != napi_ok;
+          if (!bad && has_bits) {
+            bad = napi_get_named_property(env, s, "poolBits", &bv) != napi_ok || get_bytes(env, bv, &bd, &bl) ||
+                  bl != ((size_t)pq->n_bits + 7) / 8 || bl == 0;
+            if (!bad) pq->bits = bd; /* read inside the submit below, on this thread */
+          }
+          if (bad) {
+            free_req(env, r);
+            return throw_code(env, -BGV_E_ARG);
+          }
+        }
+      }
       if (tagged) {
         napi_value av;
         uint32_t tag = 0;
-        napi_get_named_property(env, s, aggregate == 2 ? "pool" : "agg", &av);
-        if (napi_get_value_uint32(env, av, &tag) != napi_ok || tag >= (aggregate == 2 ? BGV_MAX_SIGPOOL : (1u << 20))) {
+        napi_get_named_property(env, s, aggregate >= 2 ? "pool" : "agg", &av);
+        if (napi_get_value_uint32(env, av, &tag) != napi_ok || tag >= (aggregate >= 2 ? BGV_MAX_SIGPOOL : (1u << 20))) {
           free_req(env, r);
           return throw_code(env, -BGV_E_ARG);
         }
@@ -1207,7 +1361,7 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
   CHECK(env, napi_create_reference(env, argv[0], 1, &r->ctx_ref));
   if (a->inflight++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
   int rc;
-  if (aggregate == 2) {
+  if (aggregate >= 2) {
     r->added = (uint8_t*)calloc(r->nsets ? r->nsets : 1, 1);
   } else if (aggregate) {
     r->agg96 = (uint8_t*)calloc(r->naggs ? r->naggs : 1, 96);
@@ -1224,7 +1378,10 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
       }
     r->any_span = 1;
   }
-  if (aggregate == 2) {
+  if (aggregate == 3) {
+    rc = bgv_verify_accumulate_bits_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_span ? r->spans : NULL,
+                                          r->mode, r->tags, r->poolbits, r->codes, r->added, &r->stats, verify_done, r);
+  } else if (aggregate == 2) {
     rc = bgv_verify_accumulate_async(a->c, r->jobs, r->njobs, r->sets, r->nsets, r->any_span ? r->spans : NULL, r->mode,
                                      r->tags, r->codes, r->added, &r->stats, verify_done, r);
   } else if (aggregate) {
@@ -1250,6 +1407,9 @@ static napi_value verify_start(napi_env env, napi_callback_info info, int aggreg
 static napi_value js_verify(napi_env env, napi_callback_info info) { return verify_start(env, info, 0); }
 static napi_value js_verify_aggregate(napi_env env, napi_callback_info info) { return verify_start(env, info, 1); }
 static napi_value js_verify_accumulate(napi_env env, napi_callback_info info) { return verify_start(env, info, 2); }
+static napi_value js_verify_accumulate_bits(napi_env env, napi_callback_info info) {
+  return verify_start(env, info, 3);
+}
 
 #define METHOD_ATTR ((napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable))
 
@@ -1268,6 +1428,10 @@ static napi_value init_module(napi_env env, napi_value exports) {
       {"sigpoolOpen", NULL, js_sigpool_open, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"sigpoolDropRange", NULL, js_sigpool_drop_range, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"sigpoolGet", NULL, js_sigpool_get, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"verifyAccumulateBits", NULL, js_verify_accumulate_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolOpenBits", NULL, js_sigpool_open_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolGetBits", NULL, js_sigpool_get_bits, NULL, NULL, NULL, METHOD_ATTR, NULL},
+      {"sigpoolSum", NULL, js_sigpool_sum, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"aggregatePubkeys", NULL, js_aggregate_pubkeys, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeePut", NULL, js_committee_put, NULL, NULL, NULL, METHOD_ATTR, NULL},
       {"committeeDrop", NULL, js_committee_drop, NULL, NULL, NULL, METHOD_ATTR, NULL},

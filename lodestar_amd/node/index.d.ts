@@ -87,6 +87,18 @@ export interface SameMessageSet {
   signature: Uint8Array; // 96 bytes compressed G2 (untrusted)
 }
 
+/** a pool entry (poolGetBits) or a sum of entries (poolSum) */
+export interface PoolRecord {
+  /** 0, or a negative library code (not open, nothing added yet) with signature null */
+  status: number;
+  count: number;
+  signature: Uint8Array | null;
+  /** positions of the field; the sum of the entries' for poolSum */
+  nBits: number;
+  /** ceil(nBits / 8) bytes, SSZ bit order */
+  bits: Uint8Array;
+}
+
 export interface BlsGpuVerifierOpts {
   devices?: number[];
   maxBufferedSigs?: number;
@@ -137,8 +149,31 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     poolId: number,
     opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
   ): Promise<boolean[]>;
-  /** opens the device-resident signature pool entry id (0..16383), empty */
-  poolOpen(id: number): void;
+  /**
+   * verifyAndPoolSameMessage into an entry that holds participation bits (poolOpen(id, {nBits})):
+   * each set names its position (`bit`) or its field (`bits`, ceil(nBits / 8) bytes, SSZ bit
+   * order).  `valid` is the verdict; `outcome` is what the entry did with a valid set: "added",
+   * "known" (every position already held: InsertOutcome.AlreadyKnown), "overlap" (some held, some
+   * new: not aggregated), or null (not valid, or the entry was dropped meanwhile).
+   */
+  verifyAndPoolBitsSameMessage(
+    sets: (SameMessageSet & ({bit: number} | {bits: Uint8Array}))[],
+    message: Uint8Array,
+    poolId: number,
+    opts: Omit<VerifySignatureOpts, "verifyOnMainThread"> & {nBits: number}
+  ): Promise<{valid: boolean; outcome: "added" | "known" | "overlap" | null}[]>;
+  /**
+   * opens the device-resident signature pool entry id (0..16383), empty; with nBits (1..2048) it
+   * also holds a participation field of that many positions
+   */
+  poolOpen(id: number, opts?: {nBits?: number}): void;
+  /** poolGet plus the entry's field: nBits is 0 for an entry without bits or not open */
+  poolGetBits(ids: Uint32Array | number[]): Promise<PoolRecord[]>;
+  /**
+   * sums entries on the device without changing them: per group of 1..64 ids the aggregate of every
+   * signature held and the entries' fields concatenated in list order
+   */
+  poolSum(groups: (Uint32Array | number[])[]): Promise<PoolRecord[]>;
   /** drops the live entries of ids first .. first + count - 1; returns how many there were */
   poolDropRange(first: number, count: number): number;
   /**

@@ -216,6 +216,34 @@ class BlsGpuVerifier:
         self.metrics["success_sets"] += sum(1 for c in codes if c >= 0)
         return [c == 1 and a for c, a in zip(codes, added)]
 
+    async def verify_and_pool_bits_same_message(self, sets: Sequence[tuple], message: bytes, pool_id: int,
+                                                n_bits: int, opts: Optional[VerifySignatureOpts] = None):
+        """verify_and_pool_same_message into an entry that holds participation bits (opened with
+        Context.sigpool_open(pool_id, n_bits); bgv_verify_accumulate_bits).  sets: (public key,
+        signature, member) with member the set's position in the entry (an int) or its field
+        (bytes, SSZ bit order).  One (valid, outcome) per set: valid is the verdict -- a known
+        attestation is still a valid gossip message -- and outcome "added", "known", "overlap"
+        (InsertOutcome.NewData / AlreadyKnown / NotBetterThan) or None when nothing was offered
+        to the entry.  opts and buffering as verify_signature_sets_same_message."""
+        if self.closed:
+            raise QueueError("QUEUE_ABORTED")
+        if len(sets) == 0:
+            return []
+        jobs = [([to_set_spec(ISignatureSet(SignatureSetType.single, signing_root=message, signature=sig,
+                                            pubkey=pk))], True) for pk, sig, _ in sets]
+        members = [(n_bits, m) for _, _, m in sets]
+        stats = native.BgvStats()
+
+        def call():
+            return self.ctx.verify_accumulate_bits(jobs, [pool_id] * len(jobs), members, native.MODE_WORKER, stats)
+
+        codes, outcome = await asyncio.get_running_loop().run_in_executor(None, call)
+        self._account(stats)
+        self.metrics["error_sets"] += sum(1 for c in codes if c < 0)
+        self.metrics["success_sets"] += sum(1 for c in codes if c >= 0)
+        names = {native.POOL_ADDED: "added", native.POOL_KNOWN: "known", native.POOL_OVERLAP: "overlap"}
+        return [(c == 1, names.get(o)) for c, o in zip(codes, outcome)]
+
     async def _same_message(self, sets, message: bytes, aggregate: bool):
         if self.closed:
             raise QueueError("QUEUE_ABORTED")
