@@ -382,7 +382,8 @@ int bgv_debug_uniform(bgv_ctx* ctx, const bgv_set* sets, size_t nsets, uint64_t 
  * validate=true) (state-transition/src/block/processDeposit.ts:64) for n 48-byte
  * compressed keys.  out_status[i] = 0 or -BLST code (BAD_ENCODING, POINT_NOT_ON_CURVE,
  * PK_IS_INFINITY, POINT_NOT_IN_GROUP).  out96 (may be NULL) receives the 96-byte
- * uncompressed record of every valid key (bgv_pubkeys_put / bgv_set.pk_bytes format). */
+ * uncompressed record of every valid key (bgv_pubkeys_put / bgv_set.pk_bytes format) and the
+ * infinity record (0x40, then zeros) for every other key, a decodable one outside G1 included. */
 int bgv_pubkeys_validate(bgv_ctx* ctx, const uint8_t* keys48, size_t n, int32_t* out_status, uint8_t* out96);
 
 /* Op-pool signature aggregation: bls.Signature.aggregate(sigs.map(s =>

@@ -538,6 +538,12 @@ __global__ void __launch_bounds__(64) k_prep_wide(const bgv_dslot* __restrict__ 
     const int lane = threadIdx.x;
     tg1_wide_engine e{{prog, S, RP, tr_wide_lane_c(lane), tr_wide_lane_q(lane), false}};
     tg1_mul_glv(e, slots[s].scalar);
+    // a sum outside G1 (a key taken on trust) whose schedule met an exceptional addition
+    // (bgv_tg1.h tg1_exceptional): lane 0 repeats the task with the complete one-lane formulas
+    if (tg1_exceptional(S[TG1_BANK(4) + 2])) {
+      if (lane == 0) task_pk(s, slots, pk_idx, cache, pk_bytes, rpk, pk_status, pk_agg);
+      return;
+    }
     if (lane < 3) reinterpret_cast<fp_t*>(rpk + s)[lane] = S[TG1_BANK(4) + lane];
     if (lane == 0) pk_status[s] = BGV_ST_OK;
     return;

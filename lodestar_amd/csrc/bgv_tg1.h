@@ -8,10 +8,22 @@
 // homogeneous projective coordinates with Jacobian in and out: the same point as the one-lane
 // formulas, another representative.  Both halves' prefixes stay below 2^32 < x^2, so the
 // accumulator never meets an entry or its negative once finite: the generic additions are
-// exact; P must be finite and in G1 (a cached, aggregated or validated key).
+// exact for a finite P in G1 (a validated key, or a sum of such).
+//
+// Cached keys and 96-byte records are taken on trust and may lie outside G1.  With a G1 part the
+// argument above still holds (pk + T: the accumulator and an entry differ in that part).  A point
+// of the cofactor's torsion alone (order 11 at the least; the decoding rejects order 3) can meet
+// an entry, its negative or infinity, where padd's X3 and Z3 carry the factor v = X2 Z1 - X1 Z2
+// = 0: the sum becomes (0, -u^3 Z1 Z2, 0), or (0, 0, 0) for equal points or an operand at
+// infinity, and doublings and further additions keep Z = 0 to the end.  So a result with Z = 0
+// is either r P = infinity or the trace of such a meeting (tg1_exceptional), and the caller
+// repeats the multiplication with the complete one-lane formulas (jac_mul_glv).
 #pragma once
 #include "bgv_tmiller.h"
 #include "bgv_tg1_prog.h"
+
+// tg1_mul_glv's result (its Jacobian Z) is not to be used: infinity, or an exceptional addition
+BGV_HD bool tg1_exceptional(const fp_t& z) { return fp_is_zero(z); }
 
 // r P: P in bank 1 on entry, the result in bank 4 (both Jacobian).  Tables: P, 2P, 3P in
 // banks 1-3 and E of them in banks 6-8; banks 4 / 5 the accumulator, bank 0 the entry added.
@@ -78,6 +90,7 @@ inline g1_jac tg1_mul_glv_host(const g1_jac& p, uint64_t k) {
   S[TG1_BANK(1) + 2] = p.z;
   tg1_host_engine e{tab, S};
   tg1_mul_glv(e, k);
+  if (tg1_exceptional(S[TG1_BANK(4) + 2])) return jac_mul_glv(p, k);  // as k_prep_wide's plane 3 does
   return g1_jac{S[TG1_BANK(4)], S[TG1_BANK(4) + 1], S[TG1_BANK(4) + 2]};
 }
 #endif

@@ -84,3 +84,11 @@ def b_fp12_tower(b):
 
 def buf(n):
     return ctypes.create_string_buffer(n)
+
+
+def g1_decode(L, b):
+    """(status, point or None) of a 48-byte compressed key (hs_g1_decompress) or a 96-byte record
+    (hs_g1_deserialize): 0, the BLST code, or 100 for an infinity encoding."""
+    out = buf(96)
+    rc = {48: L.hs_g1_decompress, 96: L.hs_g1_deserialize}[len(b)](out, bytes(b))
+    return rc, (b_g1(out.raw) if rc == 0 else None)

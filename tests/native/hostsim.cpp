@@ -434,6 +434,15 @@ int hs_g1_decompress(uint8_t* out, const uint8_t* in48) {
   out_g1(out, a);
   return 0;
 }
+int hs_g1_deserialize(uint8_t* out, const uint8_t* in96) {
+  g1_aff a;
+  bool inf;
+  int rc = g1_deserialize(&a, &inf, in96);
+  if (rc) return rc;
+  if (inf) return 100;
+  out_g1(out, a);
+  return 0;
+}
 void hs_g1_serialize(uint8_t* out96, const uint8_t* aff) { g1_serialize(out96, in_g1(aff), false); }
 // ---- deferred-reduction Fp2 products (bls_wide.h) against the fully reduced Karatsuba ----
 // n random operand pairs per bound pair and the extreme ones (every limb at its bound, the top
